@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: body-body interactions/s of the all-pairs N-body step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bodies B] [--fp64] [--mode fast|strict]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bodies B] [--fp64] [--mode fast|strict] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,14 @@ synthetic SHELL system the reference itself starts from.  Workload at any N GPUs
 bodies shard across ranks with one RCCL all-gather of the new positions per step, issued as position tiles by the product's own
 multi-GPU entry points (nb_comm_init_rank + nb_sharded_step_*, csrc/nbody_comm.hip); torch.distributed (gloo) only does the
 rendezvous, the barriers and the time reduction.  cuda-nbody_amd/sharded.py, the same schedule over torch.distributed, stays as
-`--exchange torch` for A/B and as the fallback.  At N=1 the line also carries "configs": the other BASELINE configs and STRICT,
-timed after the headline measurement; at N>1 it carries BASELINE configs[3] (1 048 576 bodies over the N ranks), "ranks_seen"
-(what every rank's communicator says about itself) and "diagnostics" (the same job timed with the other exchange grouping,
-one-sided, the exchange legs alone, the kernels alone) -- all taken after the timed region, under a watchdog that prints the
-line without them should they stall.  Tuning sweeps and one-rank projections live in tools/kernel_sweeps.py.
+`--exchange torch` for A/B and as the fallback.  A plain run sets up, settles the clock, warms up, times the K steps and prints
+the line; `--dump-outputs DIR` also writes what the last timed step computed.  Everything else is measured only with `--full`:
+at N=1 the line then also carries "configs" (the other BASELINE configs and STRICT, timed after the headline measurement), the
+CPU baseline, the pairwise step's per-kernel split with the clock read inside the kernel, the card's clock and power, and the
+multi-GPU projections; at N>1 it carries BASELINE configs[3] (1 048 576 bodies over the N ranks) and "diagnostics" (the same job
+timed with the other exchange grouping, one-sided, the exchange legs alone, the kernels alone) -- all taken after the timed region,
+under a watchdog that prints the line without them should they stall.  "ranks_seen" (what every rank's communicator says about
+itself) is in every N>1 line.  Tuning sweeps and one-rank projections live in tools/kernel_sweeps.py.
 
 Metric conventions are the reference's (src/nbody/compute.cpp:16-18,105-121): interactions/step = N^2
 (self-interaction counted), 20 flop per fp32 interaction, 30 per fp64.  Timing protocol: W untimed warm-up
@@ -77,6 +80,12 @@ def parse_args():
                     help="FAST on one GPU: pairwise = nb_integrate_ws_* with a caller-owned workspace (every pair of bodies evaluated once and "
                          "applied to both, csrc/nbody_pair.hip); one-sided = nb_integrate_* (every directed interaction, as the reference kernel)")
     ap.add_argument("--dump-state", type=str, default="", help="rank 0 writes its initial and final positions (.npz) here (tests)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/positions.npy (and, one rank, DIR/velocities.npy): N x 4 in the run's "
+                         "precision, a fixed sample of the bodies where that would pass 64 MB.  The timed steps start from the same bodies every run")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the CPU baseline, the other BASELINE configs, the per-kernel split and in-kernel clock, the "
+                         "card's clock and power, the multi-GPU projections (N=1) and diagnostics (N>1).  A plain run times the headline alone")
     ap.add_argument("--no-configs", action="store_true", help="skip the extra BASELINE configs timed after the headline measurement (N=1)")
     ap.add_argument("--launch-timeout", type=float, default=150.0,
                     help="plain `bench.py --gpus N`: seconds the launcher gives ONE attempt of the N ranks before ending them (see self_launch)")
@@ -233,6 +242,21 @@ def pci_address(torch, device_index):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy for every (bodies x 4) array.  Where they would pass DUMP_LIMIT_BYTES together, the same bodies of each -- a
+    sample drawn with a fixed seed, in index order -- so that two runs with the same arguments write comparable files."""
+    n = len(next(iter(arrays.values())))
+    per_body = sum(a[0].nbytes for a in arrays.values())
+    room = (DUMP_LIMIT_BYTES - 1024 * len(arrays)) // per_body  # (each .npy file's header: 128 bytes)
+    keep = slice(None) if n <= room else np.sort(np.random.default_rng(0).choice(n, room, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a[keep])
+
+
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -285,7 +309,7 @@ def main():
     # the same stream in between (seen once in round 3: two runs of one command that differed in a few bodies).
     pos0, vel0 = make_bodies(n, dtype)
     big = None  # BASELINE configs[3]'s system, for the N > 1 line (drawn now for the same reason)
-    if world > 1 and not args.no_diagnostics and args.exchange == "rccl" and args.mode == "fast" and not args.fp64 and CONFIG3_BODIES % world == 0:
+    if world > 1 and args.full and not args.no_diagnostics and args.exchange == "rccl" and args.mode == "fast" and not args.fp64 and CONFIG3_BODIES % world == 0:
         big = make_bodies(CONFIG3_BODIES if not args.rehearse_one_gpu else 65536, np.float32)
 
     pkg = entry.load_package()
@@ -541,7 +565,7 @@ def main():
     # ------------------------------------------------------------------------------------------------ the timed region
     # (a child process per rank reading two sysfs files of the rank's own card; see bench_support.ChipWatch.  Rank 0's goes into `roofline`,
     # every rank's into `ranks_seen`: on a multi-GPU node the cards need not be granted the same clock)
-    chip = ChipWatch(None if args.no_chip_watch else pci_address(torch, local_rank))
+    chip = ChipWatch(pci_address(torch, local_rank) if (args.full and not args.no_chip_watch) else None)
     if distributed:  # (BRINGUP_MARK: what the launcher waits for before it trusts an attempt with its full time)
         print(f"[bench rank {rank}] up: exchange {args.exchange}, {'pairwise across the ranks' if pairwise else 'one-sided'}, {world} rank(s)", file=sys.stderr, flush=True)
     # From idle the card ramps its clock for ~0.2 s under load (2.10 -> 2.29 GHz measured, profiles/round4_clock_and_power.txt); W warm-up
@@ -549,7 +573,7 @@ def main():
     # ~settle_seconds come first -- the SAME number on every rank (a step is collective): two steps are timed, the slowest rank's time
     # decides the count -- and the line says how many ("settle_steps").  Then W warm-up steps and exactly K timed steps, as before.
     settle_steps = 0
-    if args.settle_seconds > 0 and not args.dump_state:
+    if args.settle_seconds > 0 and not args.dump_state and not (args.dump_outputs and distributed):
         enter("clock settle (untimed steps)")
         fence()
         t_probe = time.perf_counter()
@@ -577,6 +601,12 @@ def main():
                 finish()
                 torch.cuda.synchronize()
         settle_steps += 2
+        if not distributed:
+            # the settle steps only bring the clock up; their count is measured, so the warm-up and timed steps start again from the
+            # bodies drawn above: what they compute is the same on every run (--dump-outputs)
+            bufs[0].copy_(torch.from_numpy(pos0.reshape(n, 4)))
+            vel_t.copy_(torch.from_numpy(vel0.reshape(n, 4)))
+            state["read"] = 0
     enter("warm-up steps")
     for _ in range(args.warmup):
         step()
@@ -622,12 +652,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, host_enqueue_ms = float(t[0].item()), float(t[1].item())
 
-    if args.dump_state and rank == 0:  # (the state after exactly warmup + steps steps: before anything below steps the system further)
+    if (args.dump_state or args.dump_outputs) and rank == 0:  # (the state after the last timed step: before anything below steps the system further)
         torch.cuda.synchronize()
-        final = capi_rank.pos[capi_rank.read] if capi_rank is not None else (system.positions().data_ptr() if system is not None else bufs[state["read"]].data_ptr())
-        host = np.zeros(4 * n, dtype)
-        pkg.check(lib.nb_d2h(host.ctypes.data_as(ctypes.c_void_p), final, host.nbytes, None), "nb_d2h")
-        np.savez(args.dump_state, final=host, initial=pos0)  # (the bodies the run started from, too: a test can tell a different start from a different step)
+
+        def to_host(address):
+            host = np.zeros((n, 4), dtype)
+            pkg.check(lib.nb_d2h(host.ctypes.data_as(ctypes.c_void_p), address, host.nbytes, None), "nb_d2h")
+            return host
+
+        final = to_host(capi_rank.pos[capi_rank.read] if capi_rank is not None else (system.positions().data_ptr() if system is not None else bufs[state["read"]].data_ptr()))
+        if args.dump_state:
+            np.savez(args.dump_state, final=final.reshape(-1), initial=pos0)  # (the bodies the run started from, too: a test can tell a different start from a different step)
+        if args.dump_outputs:
+            outputs = {"positions": final}
+            if world == 1:  # (several ranks: each holds the velocities of its own bodies only)
+                outputs["velocities"] = to_host(capi_rank.vel if capi_rank is not None else (system.vel.data_ptr() if system is not None else vel_t.data_ptr()))
+            write_outputs(args.dump_outputs, outputs)
 
     # ------------------------------------------------------------------------------------------------ after it: the line
     line = None
@@ -639,7 +679,7 @@ def main():
         # the dominant kernel's own duration: the pairwise step is two kernels (pair_forces, pair_finish), timed separately AFTER
         # the timed region with an event the library records between them; every other single-GPU step is one kernel
         forces_ms = finish_ms = clock_by_kernel = None
-        if pair is not None and not distributed:
+        if pair is not None and not distributed and args.full:
             clocked = pair.slices == 1 and pair.waves_per_block == 8 and pair.bodies_per_lane == (16 if not args.fp64 else 8)  # (the geometry pair_forces_clocked exists for)
             forces_ms, finish_ms, clock_by_kernel = pair_kernel_split(pkg, lib, step, stream_ptr, grid_blocks=pair.grid_blocks if clocked else 0)
         dominant_ms = forces_ms if forces_ms is not None else stream_ms_per_step
@@ -678,7 +718,8 @@ def main():
                             "tflops": per * evals / (dominant_ms * 1e-3) / 1e12, "frac": per * evals / (dominant_ms * 1e-3) / 1e12 / peak}
         roofline = {
             "bound": "valu_fp32_fma" if not args.fp64 else "valu_fp64_fma",
-            "kernel": "pair_forces" if pair is not None else ("one rank's step (all its kernels and waits)" if distributed and world > 1 else "the step's one kernel"),
+            "kernel": ("pair_forces" if forces_ms is not None else "the step's two kernels (pair_forces + pair_finish; --full times pair_forces alone)") if pair is not None else
+                      ("one rank's step (all its kernels and waits)" if distributed and world > 1 else "the step's one kernel"),
             # ALGORITHMIC flop per launch -- 20 (30) x N^2, the reference's convention (compute.cpp:16-18) -- over the
             # dominant kernel's average duration.  For the pairwise layout this is NOT a utilisation figure (each pair is evaluated
             # once, so it can pass 1): `executed` holds the flop the kernel really issues and their fraction of the same peak.
@@ -785,9 +826,9 @@ def main():
             "flops_per_interaction": flops_per,
             "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(n, dtype, pos0, vel0, args.cpu_sample_bodies)
-        if world == 1 and not args.no_configs and not args.plan:
+        if world == 1 and args.full and not args.no_configs and not args.plan:
             # The other BASELINE configs and the parity-exact mode, timed AFTER the headline measurement (never inside it)
             # so that one driver-run line carries them all.  A failure here costs only this list, never the headline.
             try:
@@ -852,7 +893,7 @@ def main():
             extra["defaults_provisional"] = ("the multi-GPU defaults (an RCCL group per position round + one tail group; the diagonal as two launches, the second one last; reaction "
                                              "rounds in ready order) were chosen on ONE GPU with a loopback rank -- no link latency, no peer to be late; diagnostics.step_ms times "
                                              "the alternatives in this very job: choose from them")
-            if not args.no_diagnostics and args.mode == "fast":
+            if args.full and not args.no_diagnostics and args.mode == "fast":
                 # the N = 1 figure of THIS process tree: rank 0 steps the whole system alone on its GPU while the others wait at the
                 # barrier -- "does N = 1 of a scaling series agree with the single-GPU bench" is then answerable from this one record
                 fence()
@@ -863,7 +904,7 @@ def main():
                 fence()
                 if rank == 0 and isinstance(extra["single_gpu_same_process"], dict) and extra["single_gpu_same_process"].get("value"):
                     extra["single_gpu_same_process"]["speedup_of_this_line"] = round(value / extra["single_gpu_same_process"]["value"], 3)
-            if not args.no_diagnostics:
+            if args.full and not args.no_diagnostics:
                 extra["diagnostics"] = multi_gpu_diagnostics(pkg, lib, dist, torch, args, capi_rank, system, sharded, launch, fence, step, finish, lend, stream_ptr,
                                                              rank, world, n, dtype, mode, dt, damping, bufs if capi_rank is not None else None,
                                                              vel_t, acc_t if capi_rank is not None else None, work_t, work_bytes, big, dev)

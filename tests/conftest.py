@@ -49,6 +49,24 @@ def load_golden(n, tag):
     return np.load(os.path.join(GOLDEN_DIR, f"shell_n{n}_{tag}.npz"), allow_pickle=False)
 
 
+def reference_randomise_sha256(config, dtype, n, cluster, velocity, seed):
+    """(SHA-256 of pos, of vel) that the reference's own randomise_bodies<T> (oracle/_ref) draws after srand(seed), as stored by
+    tests/golden/make_golden.py: the reference's answer where oracle/_ref cannot be built."""
+    import json
+
+    if not hasattr(reference_randomise_sha256, "table"):
+        with open(os.path.join(GOLDEN_DIR, "randomise_ref_sha256.json")) as f:
+            reference_randomise_sha256.table = json.load(f)
+    tag = "f32" if np.dtype(dtype) == np.float32 else "f64"
+    return tuple(reference_randomise_sha256.table[f"config={config} {tag} n={n} cluster={cluster} velocity={velocity} seed={seed}"])
+
+
+def sha256_pair(pos, vel):
+    import hashlib
+
+    return hashlib.sha256(pos.tobytes()).hexdigest(), hashlib.sha256(vel.tobytes()).hexdigest()
+
+
 def golden_steps(g):
     """the step counts a fixture holds besides 0 (N = 4096 stops at 10 to stay small)"""
     return sorted(int(k[4:]) for k in g.files if k.startswith("pos_") and k != "pos_0")

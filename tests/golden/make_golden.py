@@ -17,11 +17,16 @@ What the vectors are (and are not):
     randomise_bodies restatement (pinned to the reference's code, see above) and checks the digest.
     PARITY UNPINNED like the others: its later states are the restatement's own output -- only the initial state, through the
     digest of randomise_bodies' arrays, goes back to reference code.
+  * randomise_ref_sha256.json: the SHA-256 of the positions and velocities the REFERENCE's own randomise_bodies<T>
+    (oracle/_ref) draws for every case tests/test_oracle.py and tests/test_host_cpp.py hold the restatements to -- so that those
+    tests check against reference code where oracle/_ref cannot be built (no reference tree on the machine).
+    `python tests/golden/make_golden.py --randomise-digests` rewrites this file alone.
 Parameters: SHELL config, demo_params[0] (dt 0.016, softening 0.1, damping 1.0), cluster/velocity scale by N
 (src/nbody/compute.cpp:74-92).  Sizes: N = 8, 256, 1024 (steps 0/1/10/100) and 4096 (steps 0/1/10 -- the fixtures stay small),
 the four sizes SURVEY 8(c) names.
 """
 import hashlib
+import json
 import os
 import sys
 
@@ -81,7 +86,40 @@ def main():
             path = os.path.join(OUT, f"shell_n{n}_{tag}_compact.npz")
             np.savez_compressed(path, **data)
             print(path, os.path.getsize(path))
+    write_randomise_digests(ref)
+
+
+# the grid of tests/test_oracle.py::test_randomise_matches_reference_build (test_host_cpp.py's cases are a subset of it)
+RANDOMISE_SIZES = (1, 8, 255, 1024, 5000)
+RANDOMISE_SCALES = ((1.54, 8.0), (1.52, 2.0), (0.16, 1000.0), (6.04, 0.0))
+RANDOMISE_SEEDS = (1, 12345)
+
+
+def randomise_key(config, tag, n, cluster, velocity, seed):
+    return f"config={config} {tag} n={n} cluster={cluster} velocity={velocity} seed={seed}"
+
+
+def write_randomise_digests(ref):
+    digests = {}
+    for config in (O.NBODY_CONFIG_RANDOM, O.NBODY_CONFIG_SHELL, O.NBODY_CONFIG_EXPAND):
+        for dtype, tag in ((np.float32, "f32"), (np.float64, "f64")):
+            for n in RANDOMISE_SIZES:
+                for cluster, velocity in RANDOMISE_SCALES:
+                    for seed in RANDOMISE_SEEDS:
+                        ref.srand(seed)
+                        pos, vel = ref.randomise(config, n, cluster, velocity, dtype)
+                        digests[randomise_key(config, tag, n, cluster, velocity, seed)] = [hashlib.sha256(pos.tobytes()).hexdigest(),
+                                                                                          hashlib.sha256(vel.tobytes()).hexdigest()]
+    path = os.path.join(OUT, "randomise_ref_sha256.json")
+    with open(path, "w") as f:
+        json.dump(digests, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(path, os.path.getsize(path))
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--randomise-digests"]:
+        O.build(with_ref=True)
+        write_randomise_digests(O.ReferenceRandomise())
+    else:
+        main()

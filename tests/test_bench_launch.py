@@ -228,9 +228,8 @@ def test_one_rank_under_torchrun_runs_the_capi_sharded_step_and_matches_the_plai
 
 @pytest.mark.gpu
 def test_default_line_carries_every_baseline_config():
-    """`python bench.py` (what the driver runs): the one JSON line holds the headline AND, timed after it, the other BASELINE
-    configs and STRICT."""
-    out = run_bench("--steps", "5", "--warmup", "1", "--no-cpu-baseline")
+    """`python bench.py --full`: the one JSON line holds the headline AND, timed after it, the other BASELINE configs and STRICT."""
+    out = run_bench("--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--full")
     assert out.returncode == 0, out.stderr[-3000:]
     line = _metric_line(out.stdout)
     got = {(c["bodies"], c["dtype"], c["mode"], c["layout"]) for c in line["configs"]}
@@ -301,6 +300,56 @@ def test_default_line_carries_every_baseline_config():
 
 
 @pytest.mark.gpu
+def test_plain_line_times_the_headline_alone_and_dumps_the_same_outputs_every_run(tmp_path, oracle):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: exactly K timed steps and nothing measured besides
+    them; DIR holds the positions and velocities the last timed step wrote -- W + K steps from the start-up bodies, whatever the clock
+    settle ran before them -- the same bytes on every run, within the FAST envelope of the CPU path's trajectory."""
+    import numpy as np
+
+    from conftest import load_golden_compact
+    from test_gpu_parity import rel_err
+
+    n = 16384
+    dumps = []
+    for k in range(2):
+        out = run_bench("--steps", "6", "--warmup", "4", "--bodies", str(n), "--dump-outputs", str(tmp_path / f"run{k}"))
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = _metric_line(out.stdout)
+        assert line["steps"] == 6 and line["warmup"] == 4 and line["settle_steps"] > 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert line["config"]["step_entry_point"] == "nb_integrate_ws_*" and line["roofline"]["pair_forces_ms"] is None and line["roofline"]["chip"] is None
+        assert not {"configs", "cpu_baseline", "multi_gpu_kernel_projection"} & set(line)
+        dumps.append({name: np.load(tmp_path / f"run{k}" / f"{name}.npy") for name in ("positions", "velocities")})
+    assert sorted(os.listdir(tmp_path / "run0")) == ["positions.npy", "velocities.npy"]
+    for name in ("positions", "velocities"):
+        assert dumps[0][name].dtype == np.float32 and dumps[0][name].shape == (n, 4)
+        assert dumps[0][name].tobytes() == dumps[1][name].tobytes(), name
+    g = load_golden_compact(n, "f32", oracle)  # (the bars of tests/test_pairwise_trajectory.py after 10 steps)
+    assert rel_err(dumps[0]["positions"].reshape(-1), g["pos_10"]).max() <= 2e-5
+    assert rel_err(dumps[0]["velocities"].reshape(-1), g["vel_10"]).max() <= 2e-4
+
+
+def test_dumped_outputs_are_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.write_outputs (--dump-outputs): arrays that fit are written whole; larger ones as the same bodies of every array, in
+    index order, drawn the same on every run, under 64 MB in all."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n = 2_100_000  # fp64: 67 MB per array
+    pos = np.arange(4 * n, dtype=np.float64).reshape(n, 4)
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), {"positions": pos, "velocities": -pos})
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64e6
+    p, v = np.load(tmp_path / "a" / "positions.npy"), np.load(tmp_path / "a" / "velocities.npy")
+    assert p.dtype == np.float64 and p.shape[1] == 4 and n // 3 < len(p) < n // 2
+    assert np.array_equal(v, -p) and np.all(np.diff(p[:, 0]) > 0) and np.all(p[:, 0] % 4 == 0)
+    assert all(np.load(tmp_path / "b" / f).tobytes() == np.load(tmp_path / "a" / f).tobytes() for f in ("positions.npy", "velocities.npy"))
+    bench.write_outputs(str(tmp_path / "c"), {"positions": pos[:1000].astype(np.float32)})
+    assert np.array_equal(np.load(tmp_path / "c" / "positions.npy"), pos[:1000].astype(np.float32))
+
+
+@pytest.mark.gpu
 def test_emulated_rank_of_a_pairwise_multi_gpu_step():
     """`tools/kernel_sweeps.py --emulate-gpus 8`: one rank's kernels of the pairwise step across 8 ranks (nb_emulate_pair_rank_*),
     timed on the one GPU -- the compute side of the strong-scaling projection; and the one-sided tile schedule for comparison."""
@@ -326,7 +375,7 @@ def test_n_rank_line_rehearsed_on_one_gpu_through_the_capi(ranks):
     what it shows is that the N > 1 line comes out whole: the layout the communicator agreed on, what every rank's communicator
     says about itself, the A/B timings of the diagnostics (both exchange groupings x both layouts, the exchange legs alone, the
     kernels alone) and BASELINE configs[3]'s shape through the same communicator."""
-    out = run_bench("--gpus", str(ranks), "--rehearse-one-gpu", "--steps", "3", "--warmup", "1", "--bodies", "16384", "--no-cpu-baseline")
+    out = run_bench("--gpus", str(ranks), "--rehearse-one-gpu", "--steps", "3", "--warmup", "1", "--bodies", "16384", "--no-cpu-baseline", "--full")
     assert out.returncode == 0, out.stderr[-4000:]
     line = _metric_line(out.stdout)
     assert line["n_gpus"] == ranks and line["exchange_fallback"] is False and line["value"] > 0
@@ -439,7 +488,7 @@ def test_stalled_diagnostics_never_cost_the_headline(tmp_path):
     trigger = tmp_path / "hang_now"
     env.update({"FAKE_RCCL_HANG_WHEN_EXISTS": str(trigger), "FAKE_RCCL_TIMEOUT_S": "100"})
     child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "3", "--warmup", "1", "--bodies", "16384", "--no-cpu-baseline",
-                              "--diagnostics-timeout", "6"], stdout=open(tmp_path / "out.txt", "w"), stderr=subprocess.PIPE, text=True, env=env)
+                              "--full", "--diagnostics-timeout", "6"], stdout=open(tmp_path / "out.txt", "w"), stderr=subprocess.PIPE, text=True, env=env)
     err = []
 
     def watch():

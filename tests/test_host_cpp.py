@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import ROOT, load_golden, reference_randomise_sha256, sha256_pair
 
 PKG = os.path.join(ROOT, "cuda-nbody_amd")
 CLI = os.environ.get("NBODY_CLI", os.path.join(PKG, "nbody"))  # `make test-sanitize` points these at the ASan/UBSan builds
@@ -50,7 +50,8 @@ def host_randomise(host, config, n, cluster, velocity, dtype):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("config", [0, 1, 2])
 def test_host_randomise_bodies_bitwise(O, oracle, host, dtype, config):
-    """The product's randomise_bodies == the oracle's == (when oracle/_ref is built) the reference's own code."""
+    """The product's randomise_bodies == the oracle's == the reference's own code (its output's SHA-256 under tests/golden/, and
+    oracle/_ref itself when that is built)."""
     ref = O.ReferenceRandomise() if O.ReferenceRandomise.available() else None
     for n in (1, 8, 255, 1024, 5000):
         for cluster, velocity in ((1.54, 8.0), (1.52, 2.0), (0.16, 1000.0)):
@@ -59,6 +60,7 @@ def test_host_randomise_bodies_bitwise(O, oracle, host, dtype, config):
             oracle.srand(1)
             b = oracle.randomise(config, n, cluster, velocity, dtype)
             assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+            assert sha256_pair(*a) == reference_randomise_sha256(config, dtype, n, cluster, velocity, 1), (n, cluster, velocity)
             if ref is not None:
                 ref.srand(1)
                 c = ref.randomise(config, n, cluster, velocity, dtype)

@@ -12,7 +12,7 @@ OUT=${1:-gpurun_out/evidence}
 mkdir -p $OUT
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.txt 2>&1; rc=$?; tail -3 $OUT/pytest_gpu.txt; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 python __graft_entry__.py smoke > $OUT/smoke.txt 2>&1 || { tail -5 $OUT/smoke.txt; exit 1; }
-timeout -k 10 300 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo "bench ok: $(cut -c1-200 $OUT/bench.json)"
 timeout -k 10 300 python3 bench.py --layout one-sided --no-configs --no-cpu-baseline > $OUT/bench_one_sided.json 2> $OUT/bench_one_sided.err || exit 1
 # round 5: the real RCCL on this one GPU -- the self-loop (every byte checked) and the loopback rank next to the shipping kernels
