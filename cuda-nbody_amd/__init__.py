@@ -88,6 +88,12 @@ class LaunchPlan(ctypes.Structure):
                 ("block_threads", ctypes.c_int), ("grid_blocks", ctypes.c_uint), ("lds_bytes", ctypes.c_uint)]
 
 
+class Energy(ctypes.Structure):
+    """nb_energy_t (include/nbody_hip.h): energy, momentum and angular momentum of a state, G = 1"""
+    _fields_ = [("kinetic", ctypes.c_double), ("potential", ctypes.c_double), ("total", ctypes.c_double), ("mass", ctypes.c_double),
+                ("momentum", ctypes.c_double * 3), ("angular_momentum", ctypes.c_double * 3), ("center_of_mass", ctypes.c_double * 3)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks against the header
 _vp, _ci, _cu, _cf, _cd, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
 _P = ctypes.POINTER
@@ -162,6 +168,9 @@ SIGNATURES = {
     "nb_allgather_f64": (_ci, [_vp, _vp, _cu, _vp]),
     "nb_exchange_wait_tile": (_ci, [_vp, _ci, _vp]),
     "nb_exchange_wait_all": (_ci, [_vp, _vp]),
+    "nb_energy_workspace_bytes": (_ci, [_cu, _P(_sz)]),
+    "nb_energy_f32": (_ci, [_vp, _vp, _cu, _vp, _sz, _vp, _vp]),
+    "nb_energy_f64": (_ci, [_vp, _vp, _cu, _vp, _sz, _vp, _vp]),
     "nb_plan_f32": (_ci, [_cu, _cu, _P(LaunchPlan)]),
     "nb_plan_f64": (_ci, [_cu, _cu, _P(LaunchPlan)]),
 }
@@ -614,6 +623,36 @@ def workspace_bytes(num_bodies: int, dtype=np.float32, mode: int = NB_MODE_FAST,
     else:
         check((lib().nb_workspace_bytes_capped_f32 if f32 else lib().nb_workspace_bytes_capped_f64)(num_bodies, mode, max_bytes, ctypes.byref(need)), "nb_workspace_bytes_capped")
     return need.value
+
+
+def energy_workspace_bytes(num_bodies: int) -> int:
+    """nb_energy_workspace_bytes: scratch memory nb_energy_* needs for this many bodies (either precision)"""
+    need = _sz(0)
+    check(lib().nb_energy_workspace_bytes(num_bodies, ctypes.byref(need)), "nb_energy_workspace_bytes")
+    return need.value
+
+
+def energy(positions, velocities, num_bodies: int, dtype=np.float32, workspace=None, stream=None) -> dict:
+    """nb_energy_* of the device arrays `positions` / `velocities` (raw device addresses) with the softening^2 set for `dtype`:
+    {"kinetic", "potential", "total", "mass", "momentum", "angular_momentum", "center_of_mass"} (vectors as 3-tuples).
+    `workspace`: a DeviceBuffer of at least energy_workspace_bytes(num_bodies) bytes; None = one is allocated for the call.
+    Blocks until the result is back on the host."""
+    own = workspace is None
+    if own:
+        workspace = DeviceBuffer(energy_workspace_bytes(num_bodies))
+    result = DeviceBuffer(ctypes.sizeof(Energy))
+    check(lib().nb_stream_synchronize(None), "nb_stream_synchronize")  # (DeviceBuffer clears on the null stream; `stream` may not wait for it)
+    try:
+        fn = lib().nb_energy_f32 if np.dtype(dtype) == np.float32 else lib().nb_energy_f64
+        check(fn(positions, velocities, num_bodies, workspace.ptr, workspace.nbytes, result.ptr, stream), "nb_energy")
+        out = Energy()
+        check(lib().nb_d2h(ctypes.byref(out), result.ptr, ctypes.sizeof(Energy), stream), "nb_d2h(energy)")
+    finally:
+        result.free()
+        if own:
+            workspace.free()
+    return {"kinetic": out.kinetic, "potential": out.potential, "total": out.total, "mass": out.mass, "momentum": tuple(out.momentum),
+            "angular_momentum": tuple(out.angular_momentum), "center_of_mass": tuple(out.center_of_mass)}
 
 
 def comm_transport_info(comm) -> dict:

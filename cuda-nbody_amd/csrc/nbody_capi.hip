@@ -288,6 +288,27 @@ template <typename T> int plan_query(unsigned i_count, unsigned j_count, nb_laun
     return 0;
 }
 
+// nb_energy_*: every argument checked on the host, then two launches on `stream` (nbody_energy.hip); no lock, no synchronisation.
+// The workspace serves either precision: its size is the larger of the two plans.
+constexpr unsigned kEnergyMaxBodies = 1u << 31;
+size_t energy_workspace_bytes(unsigned n) { return std::max(nb::plan_energy<float>(n).workspace_bytes, nb::plan_energy<double>(n).workspace_bytes); }
+
+template <typename T> int energy(const T* pos, const T* vel, unsigned n, void* workspace, size_t workspace_bytes, nb_energy_t* result, T eps2, nb_stream_t stream) {
+    if (!pos || !vel || !workspace || !result || n == 0 || n > kEnergyMaxBodies) return NB_ERR_INVALID_ARGUMENT;
+    const size_t need = energy_workspace_bytes(n);
+    if (workspace_bytes < need) return NB_ERR_INVALID_ARGUMENT;
+    const auto addr = [](const void* q) { return reinterpret_cast<std::uintptr_t>(q); };
+    if (!aligned_vec4<T>(pos) || !aligned_vec4<T>(vel) || addr(workspace) % sizeof(double) != 0 || addr(result) % sizeof(double) != 0) return NB_ERR_INVALID_ARGUMENT;
+    const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T);
+    const auto overlap = [&](const void* x, std::uintptr_t x_len, const void* y, std::uintptr_t y_len) { return addr(x) < addr(y) + y_len && addr(y) < addr(x) + x_len; };
+    for (const void* body_array : {static_cast<const void*>(pos), static_cast<const void*>(vel)}) {
+        if (overlap(workspace, need, body_array, bodies) || overlap(result, sizeof(nb_energy_t), body_array, bodies)) return NB_ERR_INVALID_ARGUMENT;
+    }
+    if (overlap(workspace, need, result, sizeof(nb_energy_t))) return NB_ERR_INVALID_ARGUMENT;
+    return static_cast<int>(nb::launch_energy<T>(pos, vel, n, eps2, nb::plan_energy<T>(n), workspace, result, as_stream(stream)));
+}
+static_assert(sizeof(nb_energy_t) == 13 * sizeof(double), "13 doubles, no padding");
+
 }  // namespace
 
 namespace nb {
@@ -531,6 +552,18 @@ int nb_integrate_ws_f32(float* new_positions, const float* old_positions, float*
 int nb_integrate_ws_f64(double* new_positions, const double* old_positions, double* velocities, double dt, double damping, unsigned num_bodies, int block_size, int mode, void* workspace, size_t workspace_bytes,
                         nb_stream_t stream) {
     return integrate_ws<double>(new_positions, old_positions, velocities, dt, damping, g_softening_sq_f64.load(), num_bodies, block_size, mode, workspace, workspace_bytes, stream);
+}
+
+int nb_energy_workspace_bytes(unsigned num_bodies, size_t* bytes) {
+    if (bytes == nullptr || num_bodies == 0 || num_bodies > kEnergyMaxBodies) return NB_ERR_INVALID_ARGUMENT;
+    *bytes = energy_workspace_bytes(num_bodies);
+    return 0;
+}
+int nb_energy_f32(const float* positions, const float* velocities, unsigned num_bodies, void* workspace, size_t workspace_bytes, nb_energy_t* device_result, nb_stream_t stream) {
+    return energy<float>(positions, velocities, num_bodies, workspace, workspace_bytes, device_result, g_softening_sq_f32.load(), stream);
+}
+int nb_energy_f64(const double* positions, const double* velocities, unsigned num_bodies, void* workspace, size_t workspace_bytes, nb_energy_t* device_result, nb_stream_t stream) {
+    return energy<double>(positions, velocities, num_bodies, workspace, workspace_bytes, device_result, g_softening_sq_f64.load(), stream);
 }
 
 int nb_pair_plan_f32(unsigned num_bodies, nb_pair_plan_t* plan) { return pair_plan_query<float>(num_bodies, plan); }

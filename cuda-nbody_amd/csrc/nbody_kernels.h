@@ -7,6 +7,8 @@
 
 #include <atomic>
 
+typedef struct nb_energy nb_energy_t;  // include/nbody_hip.h
+
 namespace nb {
 
 // Dynamic LDS above 64 KiB needs an opt-in per KERNEL and per DEVICE (gfx950 has 160 KiB per CU).  The state is keyed on the
@@ -176,6 +178,18 @@ unsigned long long* pair_clock_words(size_t* bytes);
 // nb_set_pair_plan_override: 0 = automatic (defined in nbody_capi.hip; the multi-GPU layer honours it for its tiles too)
 void pair_plan_overrides(int* vectors_per_lane, int* waves, int* splits);
 
+
+// geometry of the energy diagnostics (nbody_energy.hip): a function of (N, precision) alone
+struct EnergyPlan {
+    unsigned block_bodies;   // 64 * I
+    unsigned blocks;         // NB; block a meets blocks a .. a + NB/2 (mod NB)
+    unsigned units;          // per block: partner blocks x chunks of bodies j
+    unsigned splits;         // C workgroups per block
+    unsigned records;        // NB * C fp64 records in the workspace
+    size_t   workspace_bytes;
+};
+template <typename T> EnergyPlan plan_energy(unsigned n);  // n == 0: all zero
+template <typename T> hipError_t launch_energy(const T* pos, const T* vel, unsigned n, T eps2, const EnergyPlan& p, void* workspace, nb_energy_t* out, hipStream_t stream);
 
 template <typename T> PairPlan   plan_pair(unsigned n, int cu_count, int ovr_r, int ovr_s, int ovr_c);
 // the pieces of a pairwise step, for callers that compose them themselves (nbody_comm.hip: one rank of a multi-GPU system)

@@ -3,6 +3,8 @@
 #include "integrate_nbody_hip.hpp"
 #include "randomise_bodies.hpp"
 
+#include <stdexcept>
+
 // ctor chain and softening^2 = T(softening) * T(softening): /root/reference/src/nbody/bodysystemcuda.cpp:42-58
 template <std::floating_point T>
 BodySystemHIP<T>::BodySystemHIP(unsigned int nb_bodies, unsigned int blockSize, const NBodyParams& params) : BodySystemHIP(nb_bodies, blockSize, params, std::vector<T>(nb_bodies * 4, T{0}), std::vector<T>(nb_bodies * 4, T{0})) {}
@@ -31,6 +33,8 @@ template <std::floating_point T> auto BodySystemHIP<T>::update_params(const NBod
     apply_softening();
     damping_ = active_params.damping;
 }
+
+template <std::floating_point T> auto BodySystemHIP<T>::energy() -> nb_energy_t { throw std::invalid_argument("energy: single-device body systems only"); }
 
 template class BodySystemHIP<float>;
 template class BodySystemHIP<double>;

@@ -51,6 +51,10 @@ template <std::floating_point T> class BodySystemHIP {
     auto virtual host_enqueue_ms_per_step() const noexcept -> double { return -1.0; }
     auto virtual reset_host_enqueue() noexcept -> void {}
 
+    // Extension (--energy): energy, momentum and angular momentum of the current state (nb_energy_*, on this system's device and stream;
+    // blocks until the result is on the host).  Single-device systems only: the sharded one throws std::invalid_argument.
+    auto virtual energy() -> nb_energy_t;
+
     virtual ~BodySystemHIP() = default;
 
  protected:

@@ -52,6 +52,20 @@ template <std::floating_point T, template <std::floating_point> class Storage> a
     std::swap(this->current_read_, this->current_write_);
 }
 
+// Energy of the current state: positions[read] and the velocities, with this system's softening^2, on its stream.  Mapped host
+// memory works as it is: its pointers are device pointers.
+template <std::floating_point T, template <std::floating_point> class Storage> auto BodySystemHIPStored<T, Storage>::energy() -> nb_energy_t {
+    this->apply_softening();
+    std::size_t need = 0;
+    hip_check(nb_energy_workspace_bytes(this->nb_bodies_, &need), "nb_energy_workspace_bytes");
+    if (energy_workspace_.size() < need) energy_workspace_ = DeviceArray<unsigned char>(need);
+    if (energy_result_.size() == 0) energy_result_ = DeviceArray<nb_energy_t>(1);
+    energyNbodySystem<T>(storage_.position_ptr(this->current_read_), storage_.velocity_ptr(), this->nb_bodies_, energy_workspace_.data(), energy_workspace_.size(), energy_result_.data(), this->stream());
+    nb_energy_t result{};
+    hip_check(nb_d2h(&result, energy_result_.data(), sizeof(result), this->stream()), "nb_d2h");
+    return result;
+}
+
 // The library allocates nothing (the reference's ownership rule): the body system asks how much scratch memory the current
 // mode wants for this many bodies and owns it, like its three body arrays.
 template <std::floating_point T, template <std::floating_point> class Storage> auto BodySystemHIPStored<T, Storage>::ensure_workspace() -> void {

@@ -97,6 +97,7 @@ template <std::floating_point T, template <std::floating_point> class Storage> c
     auto set_velocity(std::span<const T> data) -> void override;
 
     auto update(T deltaTime) -> void override;
+    auto energy() -> nb_energy_t override;
     auto prepare_many(T deltaTime, unsigned steps) -> void override;
     auto update_many(T deltaTime, unsigned steps) -> void override;
 
@@ -111,6 +112,10 @@ template <std::floating_point T, template <std::floating_point> class Storage> c
     DeviceArray<unsigned char> workspace_;
     std::size_t                workspace_bytes_ = 0;
     int                        workspace_mode_  = -1;
+
+    // scratch memory and result of nb_energy_* (allocated on the first energy() call)
+    DeviceArray<unsigned char> energy_workspace_;
+    DeviceArray<nb_energy_t>   energy_result_;
 
     // captured step loop (nb_graph_*): valid for one (dt, steps, read index, mode, damping, softening^2) combination
     nb_graph_t   graph_       = nullptr;

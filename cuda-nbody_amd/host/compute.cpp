@@ -117,6 +117,7 @@ auto Compute::run_benchmark(int nb_iterations) -> void {
 }
 
 auto Compute::use_graph(bool enable) -> void { compute_hip_->use_graph(enable); }
+auto Compute::energy() -> nb_energy_t { return compute_hip_->energy(); }
 
 auto Compute::compare_results(double injected_error) -> bool { return compute_hip_->compare_results(active_params_, injected_error); }
 auto Compute::report_trajectory_error(std::size_t steps) -> void { compute_hip_->report_trajectory_error(active_params_, steps); }

@@ -9,6 +9,8 @@
 
 #include "nbody_types.hpp"
 
+#include "../../include/nbody_hip.h"  // nb_energy_t
+
 #include <array>
 #include <filesystem>
 #include <memory>
@@ -52,6 +54,7 @@ class Compute {
     auto update_params() -> void;
     auto switch_precision() -> void;
     auto use_graph(bool enable) -> void;  // extension: --graph
+    auto energy() -> nb_energy_t;         // extension: --energy (nb_energy_* of the current state)
 
     // ---- what it reports ---------------------------------------------------------------------------------------
     auto nb_bodies() const noexcept { return num_bodies_; }

@@ -282,4 +282,8 @@ auto ComputeHIP::compare_results(const NBodyParams& params, double injected_erro
     return with_active([&](auto& nbody) { return compare_results(params, nbody, injected_error); });
 }
 
+auto ComputeHIP::energy() -> nb_energy_t {
+    return with_active([](auto& nbody) { return nbody.energy(); });
+}
+
 ComputeHIP::~ComputeHIP() noexcept = default;

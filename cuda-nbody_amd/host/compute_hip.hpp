@@ -59,6 +59,7 @@ class ComputeHIP {
     // the check, so that a test can see the check fail (and the process exit with 1, nbody.cpp:375-379).
     auto compare_results(const NBodyParams& params, double injected_error = 0.0) -> bool;
     auto report_trajectory_error(const NBodyParams& params, std::size_t steps) -> void;  // --compare --steps=K (extension)
+    auto energy() -> nb_energy_t;  // --energy (extension): energy and momentum of the active system's current state
 
  private:
     // calls f(system) with the active precision's body system

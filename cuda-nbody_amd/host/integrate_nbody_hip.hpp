@@ -2,6 +2,7 @@
 // the C-ABI, so BodySystem-shaped host code compiles unchanged against the HIP library:
 //   integrateNbodySystem<T>   /root/reference/src/nbody/integrate_nbody_cuda.hpp:5, def bodysystemcuda.cu:186-215
 //   set_softening_squared     decl /root/reference/src/nbody/bodysystemcuda.cpp:37-38, def bodysystemcuda.cu:46-60
+// and the extension nb_energy_* (energyNbodySystem<T>: the reference has no counterpart) under the same error policy.
 // Error behaviour is the reference's: a failed launch prints to stderr and exit(EXIT_FAILURE)
 // (bodysystemcuda.cu:204-214); a failed softening upload throws std::runtime_error (:49-59).
 #pragma once
@@ -63,6 +64,22 @@ void integrateNbodySystemWs(T* new_positions, const T* old_positions, T* velocit
     } else {
         static_assert(std::same_as<T, double>, "float or double");
         status = nb_integrate_ws_f64(new_positions, old_positions, velocities, deltaTime, damping, numBodies, blockSize, nbody_hip::integration_mode(), workspace, workspace_bytes, nullptr);
+    }
+    if (status != 0) {
+        std::fprintf(stderr, "%s(%i) : HIP error : Kernel execution failed : (%d) %s.\n", __FILE__, __LINE__, status, nb_error_string(status));
+        std::exit(EXIT_FAILURE);
+    }
+}
+
+// Energy / momentum diagnostics of a state (include/nbody_hip.h, nb_energy_*), asynchronous on `stream`: same error behaviour as a failed step.
+template <std::floating_point T>
+void energyNbodySystem(const T* positions, const T* velocities, unsigned int numBodies, void* workspace, std::size_t workspace_bytes, nb_energy_t* device_result, nb_stream_t stream) {
+    int status;
+    if constexpr (std::same_as<T, float>) {
+        status = nb_energy_f32(positions, velocities, numBodies, workspace, workspace_bytes, device_result, stream);
+    } else {
+        static_assert(std::same_as<T, double>, "float or double");
+        status = nb_energy_f64(positions, velocities, numBodies, workspace, workspace_bytes, device_result, stream);
     }
     if (status != 0) {
         std::fprintf(stderr, "%s(%i) : HIP error : Kernel execution failed : (%d) %s.\n", __FILE__, __LINE__, status, nb_error_string(status));

@@ -6,13 +6,14 @@
 //                     --tipsy=<file> -i,--iterations=<n> --blockSize=<n>      (single-dash spellings accepted too)
 //   extensions      : --numdevices=<n> | --devices=<list> (the NVIDIA sample's -numdevices, which this fork of it dropped)
 //                     --mode=fast|strict  --config=shell|random|expand  --demo=<0..6>  --steps=<n>  --dump=<file>
-//                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
+//                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 #include "compute.hpp"
 #include "integrate_nbody_hip.hpp"
 
 #include <dlfcn.h>  // (the --alloc-limit-mib test hook lives in the lab library: looked up, never linked)
 
 #include <charconv>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +52,7 @@ struct Options {
     std::optional<unsigned> seed;
     bool                  graph = false;
     bool                  no_workspace = false;
+    bool                  energy = false;  // print the energy at the start and the end of a --benchmark / --steps run
     std::size_t           workspace_mib = 0;  // 0: no bound of our own
     std::size_t           alloc_limit_mib = 0;  // test hook: device allocations above this are refused (0: none)
     std::vector<int>      devices;  // --numdevices=<n> (devices 0..n-1) or --devices=<a,b,...>: bodies sharded over several GPUs
@@ -88,6 +90,8 @@ Options:
                               (default: the body system owns a workspace and every PAIR of bodies is evaluated once)
   --workspace-mib UINT        Spend at most this many MiB on that workspace (the pair tournament is then cut into slices that share
                               one region of reaction planes; default: what the library asks for, at most a third of the device's memory)
+  --energy                    With --benchmark or --steps: print the kinetic, potential and total energy and the momentum before and
+                              after the run, and the relative drift of the total energy (one device only)
   --inject-error FLOAT        Test hook: added to body 0's x of the fast result before --compare checks it
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
@@ -148,6 +152,7 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         else if (name == "cpu") ok = flag(options.cpu);
         else if (name == "graph") ok = flag(options.graph);
         else if (name == "no-workspace" || name == "no_workspace") ok = flag(options.no_workspace);
+        else if (name == "energy") ok = flag(options.energy);
         else if (name == "numbodies") {
             const auto v = take_value();
             ok           = v && parse_number(*v, options.numbodies) && options.numbodies >= 1;
@@ -231,10 +236,18 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         if (!ok) return error("Could not parse argument: " + std::string(arg));
     }
 
+    // combinations judged once every argument is in (--numdevices may come after --energy)
+    if (options.energy && options.devices.size() > 1) return error("--energy is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
+    if (options.energy && (options.compare || options.qatest)) return error("--energy cannot be combined with --compare or --qatest (those runs step two systems)");
+
     // the reference prints this hint and the full help on every successful parse (nbody.cpp:315-316)
     std::printf("Run \" nbody - benchmark[-numbodies = <numBodies>] \" to measure performance\n");
     std::printf("%s\n", help_text);
     return std::pair(Status::OK, options);
+}
+
+auto print_energy(const char* what, const nb_energy_t& e) -> void {
+    std::printf("%s: kinetic=%.9g potential=%.9g total=%.9g momentum=%.9g,%.9g,%.9g", what, e.kinetic, e.potential, e.total, e.momentum[0], e.momentum[1], e.momentum[2]);
 }
 
 template <typename T> auto dump_state(const std::filesystem::path& file, std::span<const T> pos, std::span<const T> vel) -> void {
@@ -277,9 +290,22 @@ auto main(int argc, char** argv) -> int {
 
         compute.use_graph(cmd_options.graph);
         if (cmd_options.demo) compute.select_demo(*cmd_options.demo);
+        const auto measure_energy = cmd_options.energy && (cmd_options.benchmark || cmd_options.steps > 0);
+        const auto energy_start   = measure_energy ? std::optional<nb_energy_t>(compute.energy()) : std::nullopt;
+        // after the run's own output: the energy at the start and at the end, and how far the total drifted over `steps` steps
+        const auto report_energy = [&](std::size_t steps) {
+            if (!energy_start) return;
+            const auto end = compute.energy();
+            print_energy("energy start", *energy_start);
+            std::printf("\n");
+            const auto label = "energy end (" + std::to_string(steps) + " steps)";
+            print_energy(label.c_str(), end);
+            std::printf(" relative_drift=%.9g\n", (end.total - energy_start->total) / std::abs(energy_start->total));
+        };
         if (cmd_options.benchmark) {
             const auto nb_iterations = cmd_options.iterations == 0 ? 10 : static_cast<int>(cmd_options.iterations);
             compute.run_benchmark(nb_iterations);
+            report_energy(1 + static_cast<std::size_t>(nb_iterations));  // (run_benchmark takes one untimed step first)
             return 0;
         }
         if (compare_to_cpu) {
@@ -295,6 +321,7 @@ auto main(int argc, char** argv) -> int {
                 dump_state<float>(cmd_options.dump, compute.positions_fp32(), compute.velocities_fp32());
             }
         }
+        report_energy(cmd_options.steps);
         return 0;
     } catch (const std::invalid_argument& e) {
         std::fprintf(stderr, "ERROR: %s\n", e.what());

@@ -284,6 +284,40 @@ NB_API int nb_graph_create_ws_f64(nb_graph_t* graph, double* position_a, double*
 NB_API int nb_graph_launch(nb_graph_t graph, nb_stream_t stream);
 NB_API int nb_graph_destroy(nb_graph_t graph);
 
+/* ---- diagnostics of the state (new: the reference has no counterpart).  Energy, momentum and angular momentum of the system in
+ *  positions / velocities, for checking conservation between steps.  Units are the reference's, G = 1.  eps^2 is the value set for
+ *  that precision with nb_set_softening_sq_f32 / nb_set_softening_sq_f64, the same value the integrate calls use.  Masses are
+ *  positions[4i+3]; velocities[4i+3] is ignored, as everywhere else.
+ *
+ *  The potential is the Plummer potential whose negative gradient is exactly the force the integrate kernels apply, so with
+ *  damping = 1 its drift measures only integrator and rounding error.  It EXCLUDES the i = j term.  An energy that sums over all
+ *  ordered pairs i, j including i = j (as the numpy energy() of tests/test_gpu_parity.py does) differs from `total` by the constant
+ *  -1/2 sum_i m_i^2 / eps (eps > 0). */
+typedef struct nb_energy {
+    double kinetic;              /* 1/2 sum_i m_i |v_i|^2                                                         */
+    double potential;            /* - sum_{i<j} m_i m_j / sqrt(|p_i - p_j|^2 + eps^2)   (i = j excluded)          */
+    double total;                /* kinetic + potential                                                           */
+    double mass;                 /* sum_i m_i                                                                     */
+    double momentum[3];          /* sum_i m_i v_i                                                                 */
+    double angular_momentum[3];  /* sum_i m_i (p_i x v_i), about the origin                                       */
+    double center_of_mass[3];    /* sum_i m_i p_i / mass  (0 when mass == 0)                                      */
+} nb_energy_t;                   /* 13 doubles, 104 bytes, no padding */
+/* The caller owns all memory; the library allocates nothing.  nb_energy_workspace_bytes says how much device scratch memory a call
+ *  on num_bodies bodies needs, for either precision (pure host logic, no GPU needed; it grows no faster than N).  nb_energy_* is
+ *  asynchronous on `stream`, takes no lock and never synchronises (it can sit between steps or inside a caller's own graph
+ *  capture); `device_result` is device memory (8-byte aligned), read it back with nb_d2h.  Positions and velocities are only read;
+ *  nothing past the workspace's first nb_energy_workspace_bytes bytes and nothing outside the 104 result bytes is written.  The
+ *  result is bitwise the same on every call with the same inputs, N and precision, whatever the workspace held before, the stream or
+ *  the timing: the launch geometry is a function of (N, precision) and the reduction order is fixed (no float atomics).
+ *  NB_ERR_INVALID_ARGUMENT, before any HIP call: a null pointer, num_bodies == 0 or above 2^31, workspace_bytes below the query's
+ *  answer, a workspace or result that is not 8-byte aligned, a body array that is not vec4-aligned, or the workspace or the result
+ *  overlapping a body array or each other. */
+NB_API int nb_energy_workspace_bytes(unsigned num_bodies, size_t* bytes);
+NB_API int nb_energy_f32(const float*  positions, const float*  velocities, unsigned num_bodies,
+                         void* workspace, size_t workspace_bytes, nb_energy_t* device_result, nb_stream_t stream);
+NB_API int nb_energy_f64(const double* positions, const double* velocities, unsigned num_bodies,
+                         void* workspace, size_t workspace_bytes, nb_energy_t* device_result, nb_stream_t stream);
+
 /* ---- introspection: the launch geometry the FAST path would use for a shard (tests / DESIGN.md) ---- */
 typedef struct nb_launch_plan {
     int bodies_per_lane;   /* I  : i-bodies register-tiled per lane                  */
