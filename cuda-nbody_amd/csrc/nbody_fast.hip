@@ -107,13 +107,12 @@ __device__ __forceinline__ void interact_uniform(const typename Lane<T>::raw4 bj
     }
 }
 
-// The mass every sum of a j range is expressed in units of: the first body's, when 1/m is a well-behaved number
-// (then an equal-mass range never multiplies by a mass inside the loop), otherwise 1.
+// The mass every sum of a j range is expressed in units of: the first body's, when the sums keep their range in units of it
+// (usable_unit, nbody_lane.h: then an equal-mass range never multiplies by a mass inside the loop), otherwise 1.
 template <typename T, typename Stream> __device__ __forceinline__ T reference_mass(const Shard<T>& s, Stream bodies) {
     if (s.j_count == 0) return T(1);
     const T m = bodies[s.j_begin].w;  // (a scalar load: the value is compared with scalar registers)
-    const T a = m < 0 ? -m : m;
-    return (a >= T(0x1p-60) && a <= T(0x1p60)) ? m : T(1);  // false for NaN too
+    return usable_unit(m) ? m : T(1);
 }
 
 // T: float|double   R: vectors per lane (I = R*W bodies i)   S: waves splitting j   LPT: vec4 loads per lane per chunk

@@ -48,6 +48,26 @@ template <> struct Lane<float> {
     static __device__ __forceinline__ void  keep_in_vgpr(vec& a) { asm volatile("" : "+v"(a)); }
 };
 
+// A mass the FAST kernels may keep their sums in units of (nbody_fast.hip reference_mass, nbody_pair.hip's tile and block
+// species): a term m_j d / (d^2 + eps^2)^(3/2) counted in units of m grows or shrinks by 1/m, so m must leave the sums their
+// range.  fp32: within 2^+-20.  Over STRICT's fp32 window (|coordinate| <= 2^18, |mass| in [2^-40, 2^40], eps^2 >= 2^-39) a term
+// lies between 2^-80 and 2^78; in units of such an m it stays normal and below 2^98, which leaves 2^29 of the largest terms
+// before FLT_MAX.  (2^+-60 let a first body of mass 2^-40 lift terms of 2^78 to 2^118, and ~2 000 of them overflowed: tests/test_fast_domain.py.)  fp64 keeps
+// 2^+-60, far inside its range for STRICT's fp64 window.  False for 0, NaN and infinities.
+template <typename T> __device__ __forceinline__ bool usable_unit(T m) {
+    constexpr T lo = sizeof(T) == 4 ? T(0x1p-20) : T(0x1p-60), hi = sizeof(T) == 4 ? T(0x1p20) : T(0x1p60);
+    const T a = m < 0 ? -m : m;
+    return a >= lo && a <= hi;
+}
+
+// A mass a finished sum may be multiplied by once, when it is stored (nbody_pair.hip's block species: its reaction sums are formed
+// without masses and scaled by m_block at the store, so they are never counted in units of it and need no headroom): 2^+-60 in
+// both precisions.  False for 0, NaN and infinities.
+template <typename T> __device__ __forceinline__ bool usable_scale(T m) {
+    const T a = m < 0 ? -m : m;
+    return a >= T(0x1p-60) && a <= T(0x1p60);
+}
+
 template <> struct Lane<double> {
     using vec4                 = double4;
     typedef double raw4 __attribute__((ext_vector_type(4)));

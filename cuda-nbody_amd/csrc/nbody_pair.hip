@@ -99,12 +99,6 @@ __device__ __forceinline__ double first_lane(double x) {
 __device__ __forceinline__ float  both_halves(v2f a) { return a.x + a.y; }
 __device__ __forceinline__ double both_halves(double a) { return a; }
 
-// A mass the sums may be expressed in units of: 1/m is a well-behaved number (false for 0, NaN, infinities)
-template <typename T> __device__ __forceinline__ bool usable_unit(T m) {
-    const T a = m < 0 ? -m : m;
-    return a >= T(0x1p-60) && a <= T(0x1p60);
-}
-
 // T: float|double   R: vectors per lane (I = R*W bodies i)   S: waves of a workgroup
 // Registers and occupancy: up to R = 4 vectors per lane (fp32: eight bodies i) fit 128 VGPRs -> four waves per SIMD.  R = 8 (round 4:
 // sixteen bodies i per lane in fp32, the nine rotation moves of a step amortised over twice the arithmetic -- 4.30 instead of 4.56

@@ -59,7 +59,7 @@ template <typename T, int R, int S> __global__ __launch_bounds__(64 * S) __attri
         LT::set(pz[k / W], k % W, p.z);
         same = same && i < i_end && __builtin_bit_cast(bits, p.w) == block_bits;
     }
-    const bool block_uniform = __builtin_amdgcn_ballot_w64(!same) == 0 && usable_unit(m_block);
+    const bool block_uniform = __builtin_amdgcn_ballot_w64(!same) == 0 && usable_scale(m_block);
 #pragma unroll
     for (int r = 0; r < R; ++r) ax[r] = ay[r] = az[r] = LT::splat(0);
     vec eps2 = LT::splat(s.eps2);
