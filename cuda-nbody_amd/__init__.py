@@ -25,6 +25,9 @@ LIB_PATH = os.environ.get("NBODY_HIP_LIB", os.path.join(HERE, "libnbody_hip.so")
 # the environment) before the first lib() call makes lib() load libnbody_hip_lab.so instead -- tests/ and tools/ that need the lab
 # do that in a process of their own; the product library never exports the lab's symbols.
 LAB_LIB_PATH = os.environ.get("NBODY_HIP_LAB_LIB", os.path.join(HERE, "libnbody_hip_lab.so"))
+# Ensembles (include/nbody_hip_ensemble.h: many independent systems of one size stepped in one launch) are a third library of their
+# own objects; it shares no state with the other two and is loaded next to either of them by ensemble_lib().
+ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_ensemble.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -212,7 +215,22 @@ LAB_SIGNATURES = {
     "nb_comm_replace_side_stream": (_ci, [_vp]),
 }
 
+# include/nbody_hip_ensemble.h: exported by libnbody_hip_ensemble.so, and nothing else is
+class EnsemblePlan(ctypes.Structure):
+    """nb_ensemble_plan_t: the FAST geometry of an ensemble (every field but grid_blocks a function of N and the precision)"""
+    _fields_ = [("bodies_per_lane", ctypes.c_int), ("waves_per_group", ctypes.c_int), ("groups_per_system", ctypes.c_uint),
+                ("block_threads", ctypes.c_uint), ("lds_bytes", ctypes.c_uint), ("grid_blocks", ctypes.c_ulonglong)]
+
+
+ENSEMBLE_SIGNATURES = {
+    "nb_ensemble_plan_f32": (_ci, [_cu, _cu, _P(EnsemblePlan)]),
+    "nb_ensemble_plan_f64": (_ci, [_cu, _cu, _P(EnsemblePlan)]),
+    "nb_ensemble_integrate_f32": (_ci, [_vp, _vp, _vp, _cu, _cu, _cf, _cf, _cf, _vp, _ci, _vp]),
+    "nb_ensemble_integrate_f64": (_ci, [_vp, _vp, _vp, _cu, _cu, _cd, _cd, _cd, _vp, _ci, _vp]),
+}
+
 _lib = None
+_ensemble_lib = None
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
 
 
@@ -243,6 +261,21 @@ def lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _lib = handle
     return _lib
+
+
+def ensemble_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _ensemble_lib
+    if _ensemble_lib is None:
+        if not os.path.exists(ENSEMBLE_LIB_PATH):
+            raise FileNotFoundError(f"{ENSEMBLE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(ENSEMBLE_LIB_PATH)
+        for name, (restype, argtypes) in ENSEMBLE_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _ensemble_lib = handle
+    return _ensemble_lib
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -465,6 +498,84 @@ class BodySystemHIP:
         if self._workspace is not None:
             lib().nb_free(self._workspace)
             self._workspace = None
+
+
+def ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> EnsemblePlan:
+    """nb_ensemble_plan_*: the FAST geometry of `num_systems` systems of `num_bodies` bodies"""
+    p = EnsemblePlan()
+    fn = ensemble_lib().nb_ensemble_plan_f32 if np.dtype(dtype) == np.float32 else ensemble_lib().nb_ensemble_plan_f64
+    check(fn(num_bodies, num_systems, ctypes.byref(p)), "nb_ensemble_plan")
+    return p
+
+
+class BodyEnsembleHIP:
+    """B independent systems of N bodies on the device, stepped together by nb_ensemble_integrate_* (include/nbody_hip_ensemble.h).
+
+    Two ping-pong position arrays + one velocity array of 4*N*B T; system s holds bodies [s*N, (s+1)*N).  Positions and velocities go
+    in and out as (B, N, 4) arrays; ``update`` writes pos[1-read] from pos[read] and swaps; ``set_*`` resets read = 0."""
+
+    def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, mode: int = NB_MODE_FAST):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies, self.num_systems, self.mode = int(num_bodies), int(num_systems), mode
+        ensemble_plan(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses, before anything is allocated
+        self.shape = (self.num_systems, self.num_bodies, 4)
+        nbytes = 4 * self.num_bodies * self.num_systems * self.dtype.itemsize
+        self._pos = [DeviceBuffer(nbytes), DeviceBuffer(nbytes)]
+        self._vel = DeviceBuffer(nbytes)
+        self._params = None
+        self.current_read = 0
+
+    def _upload(self, buf: DeviceBuffer, data) -> None:
+        data = np.ascontiguousarray(data, dtype=self.dtype)
+        if data.shape != self.shape:
+            raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
+        buf.upload(data)
+
+    def set_positions(self, data) -> None:
+        self.current_read = 0
+        self._upload(self._pos[0], data)
+
+    def set_velocities(self, data) -> None:
+        self.current_read = 0
+        self._upload(self._vel, data)
+
+    def get_positions(self) -> np.ndarray:
+        return self._pos[self.current_read].download(np.empty(self.shape, dtype=self.dtype))
+
+    def get_velocities(self) -> np.ndarray:
+        return self._vel.download(np.empty(self.shape, dtype=self.dtype))
+
+    def update(self, delta_time, damping=1.0, softening_sq=None, params=None, stream=None) -> None:
+        """One step of every system.  `params`: None (every system uses delta_time, damping, softening_sq) or a (B, 4) array of
+        {dt, damping, softening^2, ignored} per system (uploaded first; the scalars are then ignored).  softening_sq None: 0.01,
+        BodySystemHIP's default (T(0.1) * T(0.1))."""
+        t = self.dtype.type
+        if softening_sq is None:
+            softening_sq = t(np.float32(0.1)) * t(np.float32(0.1))
+        table = None
+        if params is not None:
+            table = np.ascontiguousarray(params, dtype=self.dtype)
+            if table.shape != (self.num_systems, 4):
+                raise ValueError(f"params: expected shape {(self.num_systems, 4)}, got {table.shape}")
+            if self._params is None:
+                self._params = DeviceBuffer(table.nbytes)
+            self._params.upload(table)
+        fn = ensemble_lib().nb_ensemble_integrate_f32 if self.dtype == np.float32 else ensemble_lib().nb_ensemble_integrate_f64
+        scalar = np.float32 if self.dtype == np.float32 else float
+        check(fn(self._pos[1 - self.current_read].ptr, self._pos[self.current_read].ptr, self._vel.ptr, self.num_bodies, self.num_systems,
+                 scalar(delta_time), scalar(damping), scalar(softening_sq), self._params.ptr if table is not None else None, self.mode, stream),
+              "nb_ensemble_integrate")
+        self.current_read = 1 - self.current_read
+
+    def synchronize(self) -> None:
+        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._pos + [self._vel] + ([self._params] if self._params is not None else []):
+            b.free()
+        self._params = None
 
 
 class Event:

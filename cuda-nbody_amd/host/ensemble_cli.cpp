@@ -1,0 +1,70 @@
+// ensemble_cli.cpp -- `nbody --systems=<B>` (ensemble_cli.hpp)
+#include "ensemble_cli.hpp"
+
+#include "bodyensemblehip.hpp"
+#include "compute.hpp"
+#include "randomise_bodies.hpp"
+#include "text.hpp"
+
+#include <cstdio>
+#include <fstream>
+#include <stdexcept>
+#include <vector>
+
+namespace {
+
+template <typename T> auto run_typed(const EnsembleRun& run) -> void {
+    const auto n = run.num_bodies, b = run.num_systems;
+    std::vector<T> pos(4 * n * b), vel(4 * n * b);
+    {
+        // the single-system start-up state (Compute's constructor): an fp32 and an fp64 system reset with demo row 0's scales, then
+        // the active precision with the N-scaled ones -- the third segment is system 0, the next draws are systems 1 .. B-1
+        std::vector<float>  p32(4 * n), v32(4 * n);
+        std::vector<double> p64(4 * n), v64(4 * n);
+        const auto demo0 = Compute::demo_params[0];
+        randomise_bodies<float>(NBodyConfig::NBODY_CONFIG_SHELL, p32, v32, demo0.cluster_scale, demo0.velocity_scale);
+        randomise_bodies<double>(NBodyConfig::NBODY_CONFIG_SHELL, p64, v64, demo0.cluster_scale, demo0.velocity_scale);
+        auto scaled = demo0;
+        Compute::scale_params_for(n, scaled);
+        for (std::size_t s = 0; s < b; ++s) {
+            randomise_bodies<T>(run.config, std::span<T>(pos).subspan(4 * n * s, 4 * n), std::span<T>(vel).subspan(4 * n * s, 4 * n), scaled.cluster_scale, scaled.velocity_scale);
+        }
+    }
+    auto ensemble = BodyEnsembleHIP<T>(n, b, run.mode);
+    ensemble.set_positions(pos);
+    ensemble.set_velocities(vel);
+    // BodySystemHIP's conversions: dt and damping float -> T, softening^2 = T(s) * T(s)
+    const T dt = static_cast<T>(run.params.time_step), damping = static_cast<T>(run.params.damping);
+    const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
+    if (run.benchmark) {
+        ensemble.update(dt, damping, softening_sq);  // (untimed, as Compute::run_benchmark)
+        HipEvent start, stop;
+        start.record();
+        for (int i = 0; i < run.iterations; ++i) ensemble.update(dt, damping, softening_sq);
+        stop.record();
+        stop.synchronize();
+        const float milliseconds = HipEvent::elapsed_ms(start, stop);
+        const float frequency    = static_cast<float>(run.iterations) * (1000.0f / milliseconds);
+        const float interactions = static_cast<float>(static_cast<double>(b) * static_cast<double>(n) * static_cast<double>(n) * 1e-9) * frequency;
+        const int   flops        = sizeof(T) == 8 ? 30 : 20;
+        std::printf("%zu bodies x %zu systems, total time for %d iterations: %s ms\n", n, b, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
+        std::printf("= %s %s-precision GFLOP/s at %d flops per interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(), sizeof(T) == 8 ? "double" : "single", flops);
+        return;
+    }
+    for (std::size_t s = 0; s < run.steps; ++s) ensemble.update(dt, damping, softening_sq);
+    if (!run.dump.empty()) {
+        ensemble.get_positions(pos);
+        ensemble.get_velocities(vel);
+        auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
+        if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
+        out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
+        out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
+    }
+}
+
+}  // namespace
+
+auto run_ensemble(const EnsembleRun& run) -> void {
+    if (run.fp64) run_typed<double>(run); else run_typed<float>(run);
+}

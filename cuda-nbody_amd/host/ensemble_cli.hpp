@@ -1,0 +1,23 @@
+// ensemble_cli.hpp -- `nbody --systems=<B>`: B independent systems of --numbodies bodies stepped in one launch (BodyEnsembleHIP).
+#pragma once
+
+#include "nbody_types.hpp"
+
+#include <cstddef>
+#include <filesystem>
+
+struct EnsembleRun {
+    bool                  fp64 = false;
+    std::size_t           num_bodies = 0, num_systems = 0;
+    int                   mode = 0;
+    NBodyConfig           config = NBodyConfig::NBODY_CONFIG_SHELL;
+    NBodyParams           params{};         // the demo row every system runs (dt, damping, softening)
+    bool                  benchmark = false;
+    int                   iterations = 10;
+    std::size_t           steps = 0;
+    std::filesystem::path dump;
+};
+
+// Starts from the current rand() state (main has applied --seed): system 0 is the single-system start-up state (the same three
+// randomise_bodies segments), systems 1 .. B-1 the next B-1 draws of the active precision with the same scales.
+auto run_ensemble(const EnsembleRun& run) -> void;

@@ -7,6 +7,8 @@
 //   extensions      : --numdevices=<n> | --devices=<list> (the NVIDIA sample's -numdevices, which this fork of it dropped)
 //                     --mode=fast|strict  --config=shell|random|expand  --demo=<0..6>  --steps=<n>  --dump=<file>
 //                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
+//                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
+#include "ensemble_cli.hpp"
 #include "compute.hpp"
 #include "integrate_nbody_hip.hpp"
 
@@ -58,6 +60,7 @@ struct Options {
     std::vector<int>      devices;  // --numdevices=<n> (devices 0..n-1) or --devices=<a,b,...>: bodies sharded over several GPUs
     std::optional<std::size_t> demo;   // row of Compute::demo_params (the reference reaches them from the viewer's keys only)
     double                inject_error = 0.0;
+    std::size_t           systems = 0;  // --systems=<B>: an ensemble of B systems (0: one system, the reference's run)
 };
 
 constexpr auto help_text = R"(The MI355X NBody hot path (drop-in for cuda-nbody's compute path).
@@ -93,6 +96,9 @@ Options:
   --energy                    With --benchmark or --steps: print the kinetic, potential and total energy and the momentum before and
                               after the run, and the relative drift of the total energy (one device only)
   --inject-error FLOAT        Test hook: added to body 0's x of the fast result before --compare checks it
+  --systems UINT              Step this many independent systems of --numbodies (<= 65536, required) bodies in one launch: system 0
+                              is the single-system start-up state, the others the next draws; --benchmark counts B*N^2 interactions
+                              per step, --dump writes every system's positions, then every system's velocities
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
 
@@ -163,6 +169,10 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         } else if (name == "blockSize") {
             const auto v = take_value();
             ok           = v && parse_number(*v, options.block_size);
+        } else if (name == "systems") {
+            const auto v = take_value();
+            ok           = v && parse_number(*v, options.systems) && options.systems >= 1 && options.systems <= 0xFFFFFFFFu;
+            if (!ok) return error("--systems: Value not in range 1 to 4294967295");
         } else if (name == "steps") {
             const auto v = take_value();
             ok           = v && parse_number(*v, options.steps);
@@ -240,6 +250,16 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
     if (options.energy && options.devices.size() > 1) return error("--energy is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
     if (options.energy && (options.compare || options.qatest)) return error("--energy cannot be combined with --compare or --qatest (those runs step two systems)");
 
+    if (options.systems > 0) {
+        if (options.numbodies == 0) return error("--systems needs an explicit --numbodies of at most 65536 (the single-system default, blockSize * 4 * CUs, is above the ensemble limit)");
+        if (options.numbodies > 65536) return error("--systems: --numbodies must be at most 65536 (above that one system fills the GPU: run it without --systems)");
+        if (options.numbodies * options.systems > (std::size_t{1} << 31)) return error("--systems: numbodies * systems must be at most 2^31");
+        if (options.devices.size() > 1) return error("--systems is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
+        if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.energy || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
+            return error("--systems cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --energy, --no-workspace, --workspace-mib or --cpu");
+        }
+    }
+
     // the reference prints this hint and the full help on every successful parse (nbody.cpp:315-316)
     std::printf("Run \" nbody - benchmark[-numbodies = <numBodies>] \" to measure performance\n");
     std::printf("%s\n", help_text);
@@ -278,6 +298,23 @@ auto main(int argc, char** argv) -> int {
             const auto limit = reinterpret_cast<SetLimit>(dlsym(RTLD_DEFAULT, "nb_set_alloc_limit"));
             if (limit == nullptr) throw std::invalid_argument("--alloc-limit-mib is a test hook of the lab library: run with LD_PRELOAD=libnbody_hip_lab.so");
             (void)limit(cmd_options.alloc_limit_mib << 20);
+        }
+
+        if (cmd_options.systems > 0) {
+            if (!cmd_options.benchmark && cmd_options.steps == 0 && cmd_options.dump.empty()) throw std::invalid_argument("--systems: pass --benchmark or --steps/--dump");
+            auto run        = EnsembleRun{};
+            run.fp64        = cmd_options.fp64;
+            run.num_bodies  = cmd_options.numbodies;
+            run.num_systems = cmd_options.systems;
+            run.mode        = cmd_options.mode;
+            run.config      = cmd_options.config;
+            run.params      = Compute::demo_params[cmd_options.demo.value_or(0)];
+            run.benchmark   = cmd_options.benchmark;
+            run.iterations  = cmd_options.iterations == 0 ? 10 : static_cast<int>(cmd_options.iterations);
+            run.steps       = cmd_options.steps;
+            run.dump        = cmd_options.dump;
+            run_ensemble(run);
+            return 0;
         }
 
         const auto compare_to_cpu = (cmd_options.compare || cmd_options.qatest) && (!cmd_options.cpu);
