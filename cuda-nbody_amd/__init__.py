@@ -28,6 +28,8 @@ LAB_LIB_PATH = os.environ.get("NBODY_HIP_LAB_LIB", os.path.join(HERE, "libnbody_
 # Ensembles (include/nbody_hip_ensemble.h: many independent systems of one size stepped in one launch) are a third library of their
 # own objects; it shares no state with the other two and is loaded next to either of them by ensemble_lib().
 ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_ensemble.so"))
+# 4th-order Hermite steps (include/nbody_hip_hermite.h) are a fourth library on the same terms, loaded by hermite_lib().
+HERMITE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_LIB", os.path.join(HERE, "libnbody_hip_hermite.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -229,8 +231,31 @@ ENSEMBLE_SIGNATURES = {
     "nb_ensemble_integrate_f64": (_ci, [_vp, _vp, _vp, _cu, _cu, _cd, _cd, _cd, _vp, _ci, _vp]),
 }
 
+
+# include/nbody_hip_hermite.h: exported by libnbody_hip_hermite.so, and nothing else is
+class HermitePlan(ctypes.Structure):
+    """nb_hermite_plan_t: the geometry of the acceleration + jerk kernel, a function of N and the precision"""
+    _fields_ = [("bodies_per_lane", ctypes.c_int), ("waves_per_group", ctypes.c_int), ("unroll", ctypes.c_int),
+                ("groups", ctypes.c_uint), ("block_threads", ctypes.c_uint), ("lds_bytes", ctypes.c_uint)]
+
+
+HERMITE_MAX_BODIES = 1 << 26
+HERMITE_TIMESTEP_SCRATCH_BYTES = 8192
+HERMITE_SIGNATURES = {
+    "nb_hermite_workspace_bytes": (_ci, [_cu, _cu, _P(_sz)]),
+    "nb_hermite_plan_f32": (_ci, [_cu, _P(HermitePlan)]),
+    "nb_hermite_plan_f64": (_ci, [_cu, _P(HermitePlan)]),
+    "nb_hermite_eval_f32": (_ci, [_vp, _vp, _vp, _vp, _cu, _cf, _vp]),
+    "nb_hermite_eval_f64": (_ci, [_vp, _vp, _vp, _vp, _cu, _cd, _vp]),
+    "nb_hermite_step_f32": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cf, _cf, _vp]),
+    "nb_hermite_step_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cd, _cd, _vp]),
+    "nb_hermite_timestep_f32": (_ci, [_vp, _vp, _cu, _cf, _vp, _vp, _sz, _vp]),
+    "nb_hermite_timestep_f64": (_ci, [_vp, _vp, _cu, _cd, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 _ensemble_lib = None
+_hermite_lib = None
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
 
 
@@ -276,6 +301,21 @@ def ensemble_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _ensemble_lib = handle
     return _ensemble_lib
+
+
+def hermite_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _hermite_lib
+    if _hermite_lib is None:
+        if not os.path.exists(HERMITE_LIB_PATH):
+            raise FileNotFoundError(f"{HERMITE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(HERMITE_LIB_PATH)
+        for name, (restype, argtypes) in HERMITE_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _hermite_lib = handle
+    return _hermite_lib
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -576,6 +616,95 @@ class BodyEnsembleHIP:
         for b in self._pos + [self._vel] + ([self._params] if self._params is not None else []):
             b.free()
         self._params = None
+
+
+def hermite_plan(num_bodies: int, dtype=np.float32) -> HermitePlan:
+    """nb_hermite_plan_*: the geometry of the acceleration + jerk kernel for `num_bodies` bodies"""
+    p = HermitePlan()
+    fn = hermite_lib().nb_hermite_plan_f32 if np.dtype(dtype) == np.float32 else hermite_lib().nb_hermite_plan_f64
+    check(fn(num_bodies, ctypes.byref(p)), "nb_hermite_plan")
+    return p
+
+
+def hermite_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(hermite_lib().nb_hermite_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_hermite_workspace_bytes")
+    return out.value
+
+
+class HermiteSystem:
+    """One system of N bodies on the device, stepped by the 4th-order Hermite scheme of include/nbody_hip_hermite.h.
+
+    Positions (stepped in place: the call allows new == old), velocities, accelerations and jerks of 4*N T, the workspace and the
+    time-step scalar are owned here.  ``set_state`` uploads (N, 4) positions {x, y, z, m} and velocities; ``eval`` fills the stored
+    accelerations and jerks from the stored state (what starts a run); ``step(dt)`` takes one step; ``suggested_dt(eta)`` reads
+    eta * min |a| / |jerk| of the stored derivatives back."""
+
+    def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies = int(num_bodies)
+        t = self.dtype.type
+        self.softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else t(softening_sq)
+        self._workspace_bytes = hermite_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
+        self.shape = (self.num_bodies, 4)
+        nbytes = 4 * self.num_bodies * self.dtype.itemsize
+        self._pos, self._vel, self._acc, self._jerk = (DeviceBuffer(nbytes) for _ in range(4))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._scratch = DeviceBuffer(HERMITE_TIMESTEP_SCRATCH_BYTES)
+        self._dt = DeviceBuffer(8)
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+
+    def _buffers(self):
+        return [self._pos, self._vel, self._acc, self._jerk, self._workspace, self._scratch, self._dt]
+
+    def set_state(self, positions, velocities) -> None:
+        for buf, data in ((self._pos, positions), (self._vel, velocities)):
+            data = np.ascontiguousarray(data, dtype=self.dtype)
+            if data.shape != self.shape:
+                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
+            buf.upload(data)
+
+    def eval(self, stream=None) -> None:
+        fn = getattr(hermite_lib(), "nb_hermite_eval_" + self._suffix)
+        check(fn(self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self._scalar(self.softening_sq), stream), "nb_hermite_eval")
+
+    def step(self, delta_time, stream=None) -> None:
+        fn = getattr(hermite_lib(), "nb_hermite_step_" + self._suffix)
+        check(fn(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
+                 self._scalar(delta_time), self._scalar(self.softening_sq), stream), "nb_hermite_step")
+
+    def suggested_dt(self, eta, stream=None):
+        fn = getattr(hermite_lib(), "nb_hermite_timestep_" + self._suffix)
+        check(fn(self._acc.ptr, self._jerk.ptr, self.num_bodies, self._scalar(eta), self._dt.ptr, self._scratch.ptr, HERMITE_TIMESTEP_SCRATCH_BYTES, stream),
+              "nb_hermite_timestep")
+        out = np.empty(1, dtype=self.dtype)
+        check(lib().nb_d2h(out.ctypes.data_as(_vp), self._dt.ptr, out.nbytes, stream), "nb_d2h")
+        return out[0]
+
+    def _download(self, buf: DeviceBuffer) -> np.ndarray:
+        return buf.download(np.empty(self.shape, dtype=self.dtype))
+
+    def get_positions(self) -> np.ndarray:
+        return self._download(self._pos)
+
+    def get_velocities(self) -> np.ndarray:
+        return self._download(self._vel)
+
+    def get_accelerations(self) -> np.ndarray:
+        return self._download(self._acc)
+
+    def get_jerks(self) -> np.ndarray:
+        return self._download(self._jerk)
+
+    def synchronize(self) -> None:
+        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
 
 
 class Event:

@@ -1,0 +1,464 @@
+// hermite_eval.hip -- the kernels of libnbody_hip_hermite.so (include/nbody_hip_hermite.h): accelerations AND jerks of a system,
+// the 4th-order Hermite predictor and corrector around them, and the shared time step.  gfx950 only; FMA contraction on.
+//
+// hermite_eval<T, S, STEP> is one-sided, on the plan of the wave-stream kernel (nbody_fast_stream.inc): a lane holds one vector of
+// bodies i (fp32: a packed pair -> v_pk_*_f32; fp64: one body) -- position, velocity, acceleration sum and jerk sum, 12 vectors --,
+// the bodies j are wave-uniform, come in through scalar loads U at a time (one group ahead of the one being computed, two register
+// sets) and enter the packed subtractions as scalar operands; the S waves of a workgroup share the bodies i, split the bodies j by
+// chunks of 128 (chunk c -> wave c mod S) and fold their sums through LDS in a fixed order.  No LDS access and no barrier inside
+// the streaming loops, no atomics anywhere, no scratch, <= 128 VGPRs.
+//
+// Per interaction, r = x_j - x_i, w = v_j - v_i, s2 = r.r + eps2:
+//     k = m_j s^-3,   a += k r,   jerk += k (w - 3 (r.w) s^-2 r)
+// fp32: 25 packed ops + 2 v_rsq_f32 per packed pair in the loop without the mass multiply, 26 with it.
+//
+// Sums.  A register sum collects at most 8 chunks (1 024 bodies j) of ONE form -- "unit": every mass of the chunk is the reference
+// mass (the first body's, when usable_unit allows), no multiply in the loop; "mixed": the raw mass multiplies in the loop -- and is
+// then added to the lane's second-level sum, scaled once (1, or 1 / m_ref).  Two levels of <= 1 024 and <= N / (1 024 S) + form
+// changes terms keep an fp32 sum at a few 1e-6 of its term magnitudes for any N.  The order depends on (N, precision) and the
+// masses alone, so results are bit-identical from call to call, stream to stream and device to device.
+#include "hermite_kernels.h"
+
+namespace nb {
+namespace {
+
+#include "nbody_lane.h"
+
+constexpr int kChunk      = 128;  // bodies j per wave and chunk
+constexpr int kFlushEvery = 8;    // chunks a register sum may collect
+template <typename T> constexpr int unroll_for() { return sizeof(T) == 8 ? 2 : 4; }  // U: a body j is 8 (fp32) / 16 (fp64) scalar registers
+
+// s^-2 and s^-3 from s2.  fp32: v_rsq_f32 (1 ulp) and two products.  fp64: the v_rsq_f64 seed y0 (relative error <= 2^-23) and, with
+// r = 1 - s2 y0^2 (|r| <= 2^-22), the series of Lane<double>::coupling for y0^3 (1-r)^(-3/2) and y0^2 (1 + r + r^2) for y0^2 / (1-r).
+template <typename T> struct Powers;
+template <> struct Powers<float> {
+    using vec = Lane<float>::vec;
+    static __device__ __forceinline__ void of(vec s2, const Lane<float>::Consts&, vec& inv2, vec& inv3) {
+        const vec inv = vec{__builtin_amdgcn_rsqf(s2.x), __builtin_amdgcn_rsqf(s2.y)};
+        inv2          = inv * inv;
+        inv3          = inv * inv2;
+    }
+};
+template <> struct Powers<double> {
+    static __device__ __forceinline__ void of(double s2, const Lane<double>::Consts& k, double& inv2, double& inv3) {
+        const double y0 = __builtin_amdgcn_rsq(s2);
+        const double t0 = y0 * y0;
+        const double r  = __builtin_fma(-s2, t0, 1.0);
+        const double c  = y0 * t0;
+        const double w  = r * __builtin_fma(r, k.c1875, k.c15);
+        inv3            = __builtin_fma(c, w, c);
+        const double q  = __builtin_fma(r, r, r);
+        inv2            = __builtin_fma(t0, q, t0);
+    }
+};
+
+template <typename T> struct BodyJ {
+    typename Lane<T>::raw4 p, v;  // {x, y, z, m}, {vx, vy, vz, -} in scalar registers
+};
+
+template <typename T, int S, bool STEP>
+__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_eval(HermiteArgs<T> a) {
+    using LT            = Lane<T>;
+    using vec4          = typename LT::vec4;
+    using vec           = typename LT::vec;
+    using raw4          = typename LT::raw4;
+    using bits          = typename LT::bits;
+    constexpr int W     = LT::W;  // bodies i per lane
+    constexpr int U     = unroll_for<T>();
+    constexpr int CH    = kChunk;
+    constexpr int LPT   = CH / 64;
+    constexpr int STRIDE = STEP ? 2 : 1;  // vec4 per body where the bodies are read
+    static_assert(CH % U == 0, "the streaming loop is unrolled by U");
+    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx4/x8/x16
+
+    const T* const   pos_base = STEP ? a.state8 : a.pos;
+    const T* const   vel_base = STEP ? a.state8 + 4 : a.vel_in;
+    const stream_ptr jp       = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(pos_base));
+    const stream_ptr jv       = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(vel_base));
+    const unsigned   n        = a.n;
+    const int        tid      = threadIdx.x;
+    const int        wave     = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int        lane     = tid & 63;
+
+    // bodies i of this lane: block_base + k*64 + lane (coalesced across the lanes of a wave)
+    const unsigned block_base = blockIdx.x * (64 * W);
+    vec            px, py, pz, vx, vy, vz;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned local = block_base + k * 64 + lane;
+        const size_t   i     = local < n ? local : n - 1;
+        const vec4     p     = reinterpret_cast<const vec4*>(pos_base)[i * STRIDE];
+        const vec4     v     = reinterpret_cast<const vec4*>(vel_base)[i * STRIDE];
+        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
+        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
+    }
+    const T    m_first  = jp[0].w;  // (a scalar load)
+    const T    m_ref    = usable_unit(m_first) ? m_first : T(1);
+    const T    inv_mref = T(1) / m_ref;
+    const bits unit_bits = __builtin_bit_cast(bits, m_ref);
+    vec        eps2     = LT::splat(a.eps2);
+    LT::keep_in_vgpr(eps2);
+    const vec minus3 = LT::splat(T(-3));
+    const typename LT::Consts consts = LT::make_consts();
+
+    // sums: ax ay az jx jy jz.  `first`: the register sum of the current form; `second`: the lane's second-level sum, in units of m_ref
+    vec first[6], second[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) first[q] = second[q] = LT::splat(0);
+
+    const unsigned n_chunks = (n + CH - 1) / CH;
+
+    // Is every mass of chunk c the reference mass?  Each lane looks at LPT masses with an ordinary vector load, one chunk ahead.
+    // (A chunk that is not a whole number of groups -- the last -- takes the mixed loop, and its odd bodies go one by one.)
+    auto chunk_is_unit = [&](unsigned c) -> bool {
+        const unsigned first_j = c * CH;
+        bool           same    = n - first_j >= static_cast<unsigned>(CH) || (n - first_j) % U == 0;
+#pragma unroll
+        for (int r = 0; r < LPT; ++r) {
+            const unsigned j = first_j + r * 64 + lane;
+            same             = same && (j >= n || __builtin_bit_cast(bits, pos_base[(4 * STRIDE) * static_cast<size_t>(j < n ? j : first_j) + 3]) == unit_bits);
+        }
+        return __builtin_amdgcn_ballot_w64(!same) == 0;
+    };
+    auto group = [&](size_t j0, BodyJ<T> (&b)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if constexpr (STEP) {
+                b[u].p = jp[2 * (j0 + u)], b[u].v = jp[2 * (j0 + u) + 1];  // adjacent: one s_load_dwordx8 / x16
+            } else {
+                b[u].p = jp[j0 + u], b[u].v = jv[j0 + u];
+            }
+        }
+    };
+
+    // UB bodies j against the lane's vector of bodies i, written stage by stage: UB independent chains in flight
+    auto compute = [&]<bool UNIT, int UB>(const BodyJ<T>* b, vec (&sum)[6]) {
+        vec dx[UB], dy[UB], dz[UB], ex[UB], ey[UB], ez[UB], s2[UB], rv[UB], k3[UB];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            dx[u] = LT::splat(b[u].p.x) - px, dy[u] = LT::splat(b[u].p.y) - py, dz[u] = LT::splat(b[u].p.z) - pz;
+            ex[u] = LT::splat(b[u].v.x) - vx, ey[u] = LT::splat(b[u].v.y) - vy, ez[u] = LT::splat(b[u].v.z) - vz;
+        }
+#pragma unroll
+        for (int u = 0; u < UB; ++u) s2[u] = LT::fma(dx[u], dx[u], eps2), rv[u] = dx[u] * ex[u];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) s2[u] = LT::fma(dy[u], dy[u], s2[u]), rv[u] = LT::fma(dy[u], ey[u], rv[u]);
+#pragma unroll
+        for (int u = 0; u < UB; ++u) s2[u] = LT::fma(dz[u], dz[u], s2[u]), rv[u] = LT::fma(dz[u], ez[u], rv[u]);
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            vec inv2;
+            Powers<T>::of(s2[u], consts, inv2, k3[u]);
+            rv[u] = (rv[u] * inv2) * minus3;  // -3 (r.w) / s^2
+            if constexpr (!UNIT) k3[u] = k3[u] * LT::splat(b[u].p.w);
+        }
+#pragma unroll
+        for (int u = 0; u < UB; ++u) ex[u] = LT::fma(rv[u], dx[u], ex[u]), ey[u] = LT::fma(rv[u], dy[u], ey[u]), ez[u] = LT::fma(rv[u], dz[u], ez[u]);
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+            sum[0] = LT::fma(dx[u], k3[u], sum[0]), sum[1] = LT::fma(dy[u], k3[u], sum[1]), sum[2] = LT::fma(dz[u], k3[u], sum[2]);
+            sum[3] = LT::fma(ex[u], k3[u], sum[3]), sum[4] = LT::fma(ey[u], k3[u], sum[4]), sum[5] = LT::fma(ez[u], k3[u], sum[5]);
+        }
+    };
+    // a group of U bodies j in stage blocks of UB: fp32 2 x 2 (four chains' temporaries at once took the kernel to 127 VGPRs, and the
+    // S = 1 instantiation into scratch; two blocks of two compile to 93 - 95), fp64 one block of 2
+    constexpr int UB = sizeof(T) == 8 ? U : U / 2;
+    auto whole = [&]<bool UNIT>(const BodyJ<T> (&b)[U]) {
+#pragma unroll
+        for (int h = 0; h < U; h += UB) compute.template operator()<UNIT, UB>(b + h, first);
+    };
+    auto arrived = [](const BodyJ<T> (&b)[U]) { asm volatile("" : : "s"(b[0].p) : "memory"); };  // what follows is issued after the set's wait
+    // b0 holds (or is loading) group 0 of the chunk at body `chunk`; on return it is loading the first group at body `next`
+    auto stream = [&]<bool UNIT>(size_t chunk, unsigned groups, size_t next, BodyJ<T> (&b0)[U], BodyJ<T> (&b1)[U]) {
+        unsigned g = 0;
+#pragma unroll 1
+        for (; g + 2 <= groups; g += 2) {
+            arrived(b0);
+            group(chunk + (g + 1) * U, b1);
+            __builtin_amdgcn_sched_barrier(0);  // (the load stays ahead of the compute it overlaps)
+            whole.template operator()<UNIT>(b0);
+            arrived(b1);
+            group(g + 2 < groups ? chunk + (g + 2) * U : next, b0);
+            __builtin_amdgcn_sched_barrier(0);
+            whole.template operator()<UNIT>(b1);
+        }
+        if (g < groups) whole.template operator()<UNIT>(b0);  // (odd count: the ragged last chunk, nothing follows it)
+    };
+    T    pending_scale = T(1);  // what `first` is still to be multiplied by
+    auto flush         = [&]() {
+        const vec scale = LT::splat(pending_scale);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) second[q] = LT::fma(first[q], scale, second[q]), first[q] = LT::splat(0);
+    };
+
+    // The SIMD arbiter is oldest-first: left alone, the waves that share a SIMD finish equal shares of work one after the other and
+    // the last runs alone at a lower issue rate (nbody_fast_stream.inc has the measurements).  As there, each wave publishes how many
+    // chunks it has done; one that is level with the slowest wave of ITS SIMD runs at priority 3, one that is ahead at 0.  The
+    // chunk -> wave assignment stays static, so no result bit depends on it.  (Plain LDS words, one writer each; a stale read only
+    // delays a priority change.)
+    __shared__ unsigned progress[4 * 8];  // [SIMD][wave of the workgroup]: chunks done; 0xffffffff: not on this SIMD, or finished
+    if (tid < 32) progress[tid] = 0xffffffffu;
+    __syncthreads();
+    const unsigned           simd = static_cast<unsigned>(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4));  // HW_REG_HW_ID[5:4] = SIMD_ID
+    volatile unsigned* const mine = progress + simd * 8;
+    unsigned                 done = 0;
+    if (lane == 0) mine[wave] = 0;
+
+    unsigned c       = wave;  // wave w streams chunks w, w+S, w+2S, ...
+    bool     unit    = c < n_chunks ? chunk_is_unit(c) : false;
+    bool     is_unit = true;  // the form `first` holds
+    unsigned held    = 0;     // chunks in `first`
+    BodyJ<T> b0[U], b1[U];
+    if (c < n_chunks && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
+    for (; c < n_chunks; c += S) {
+        const bool next_unit = (c + S) < n_chunks ? chunk_is_unit(c + S) : false;  // (its loads are in flight across the compute below)
+        if constexpr (S > 1) {
+            unsigned least = done;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) least = min(least, mine[q]);
+            if (static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(least))) >= done) {
+                __builtin_amdgcn_s_setprio(3);
+            } else {
+                __builtin_amdgcn_s_setprio(0);
+            }
+        }
+        const unsigned first_j = c * CH;
+        const unsigned count   = min(static_cast<unsigned>(CH), n - first_j);
+        const unsigned groups  = count / U;
+        // the wave's next chunk, when it has a whole group (else anything readable: the set is not used again)
+        const size_t next = ((c + S) < n_chunks && n - (first_j + S * CH) >= static_cast<unsigned>(U)) ? static_cast<size_t>(first_j) + S * CH : first_j;
+        if (unit != is_unit || held == kFlushEvery) {
+            flush();
+            is_unit = unit, pending_scale = unit ? T(1) : inv_mref, held = 0;
+        }
+        if (groups > 0) {
+            if (unit) {
+                stream.template operator()<true>(first_j, groups, next, b0, b1);
+            } else {
+                stream.template operator()<false>(first_j, groups, next, b0, b1);
+            }
+        }
+#pragma unroll 1
+        for (unsigned jj = groups * U; jj < count; ++jj) {  // ragged end of the range (a mixed chunk)
+            BodyJ<T> one[1];
+            if constexpr (STEP) {
+                one[0].p = jp[2 * (static_cast<size_t>(first_j) + jj)], one[0].v = jp[2 * (static_cast<size_t>(first_j) + jj) + 1];
+            } else {
+                one[0].p = jp[static_cast<size_t>(first_j) + jj], one[0].v = jv[static_cast<size_t>(first_j) + jj];
+            }
+            compute.template operator()<false, 1>(one, first);
+        }
+        ++held;
+        unit = next_unit;
+        ++done;
+        if (lane == 0) mine[wave] = done;
+    }
+    if (lane == 0) mine[wave] = 0xffffffffu;  // finished: never the one the others defer to
+    __builtin_amdgcn_s_setprio(0);
+    flush();
+
+    // fold the S partial sums (waves 1..S-1 -> wave 0) through LDS, fixed order
+    __shared__ T red[(S > 1 ? S - 1 : 1) * 6 * W * 64];
+    if (wave > 0) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) red[(((wave - 1) * 6 + q) * W + k) * 64 + lane] = LT::get(second[q], k);
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+#pragma unroll 1
+    for (int g = 1; g < S; ++g) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) LT::set(second[q], k, LT::get(second[q], k) + red[(((g - 1) * 6 + q) * W + k) * 64 + lane]);
+        }
+    }
+
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned local = block_base + k * 64 + lane;
+        if (local >= n) continue;
+        const size_t i = local;
+        vec4         a1, j1;
+        a1.x = LT::get(second[0], k) * m_ref, a1.y = LT::get(second[1], k) * m_ref, a1.z = LT::get(second[2], k) * m_ref, a1.w = 0;
+        j1.x = LT::get(second[3], k) * m_ref, j1.y = LT::get(second[4], k) * m_ref, j1.z = LT::get(second[5], k) * m_ref, j1.w = 0;
+        if constexpr (STEP) {
+            // the corrector:  v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,   x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12
+            const T    h = a.dt * T(0.5), d12 = a.dt * a.dt * (T(1) / T(12));
+            const vec4 x  = reinterpret_cast<const vec4*>(a.old_pos)[i];
+            vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
+            const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
+            const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
+            vec4       x1;
+            const T    v1x = __builtin_fma(d12, j0.x - j1.x, __builtin_fma(h, a0.x + a1.x, v.x));
+            const T    v1y = __builtin_fma(d12, j0.y - j1.y, __builtin_fma(h, a0.y + a1.y, v.y));
+            const T    v1z = __builtin_fma(d12, j0.z - j1.z, __builtin_fma(h, a0.z + a1.z, v.z));
+            x1.x = __builtin_fma(d12, a0.x - a1.x, __builtin_fma(h, v.x + v1x, x.x));
+            x1.y = __builtin_fma(d12, a0.y - a1.y, __builtin_fma(h, v.y + v1y, x.y));
+            x1.z = __builtin_fma(d12, a0.z - a1.z, __builtin_fma(h, v.z + v1z, x.z));
+            x1.w = x.w;
+            v.x = v1x, v.y = v1y, v.z = v1z;
+            reinterpret_cast<vec4*>(a.new_pos)[i] = x1;
+            reinterpret_cast<vec4*>(a.vel)[i]     = v;
+        }
+        reinterpret_cast<vec4*>(a.acc)[i]  = a1;
+        reinterpret_cast<vec4*>(a.jerk)[i] = j1;
+    }
+}
+
+// The predictor: x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2 -> state8 {x_p, m, v_p, 0}.  HBM-bound.
+template <typename T> __global__ __launch_bounds__(256) void hermite_predict(const T* pos, const T* vel, const T* acc, const T* jerk, T* state8, unsigned n, T dt) {
+    using vec4       = typename Lane<T>::vec4;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const vec4 x = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i];
+    const vec4 a = reinterpret_cast<const vec4*>(acc)[i], j = reinterpret_cast<const vec4*>(jerk)[i];
+    const T    h = dt * T(0.5), t = dt * (T(1) / T(3));
+    vec4       xp, vp;
+    xp.x = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.x, a.x), v.x), x.x);
+    xp.y = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.y, a.y), v.y), x.y);
+    xp.z = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.z, a.z), v.z), x.z);
+    xp.w = x.w;
+    vp.x = __builtin_fma(dt, __builtin_fma(h, j.x, a.x), v.x);
+    vp.y = __builtin_fma(dt, __builtin_fma(h, j.y, a.y), v.y);
+    vp.z = __builtin_fma(dt, __builtin_fma(h, j.z, a.z), v.z);
+    vp.w = 0;
+    reinterpret_cast<vec4*>(state8)[2 * static_cast<size_t>(i)]     = xp;
+    reinterpret_cast<vec4*>(state8)[2 * static_cast<size_t>(i) + 1] = vp;
+}
+
+// |a|^2 / |jerk|^2 of one body as a double good to ~1 ulp.  fp32 inputs: plain double arithmetic is exact enough.  fp64 inputs: the
+// two sums of squares as unevaluated pairs (products split by FMA, sums by TwoSum), then one correction step on the quotient.
+__device__ __forceinline__ void two_sum(double x, double y, double& s, double& e) {
+    s              = x + y;
+    const double b = s - x;
+    e              = (x - (s - b)) + (y - b);
+}
+__device__ __forceinline__ void norm2_pair(double x, double y, double z, double& hi, double& lo) {
+    const double px = x * x, py = y * y, pz = z * z;
+    const double ex = __builtin_fma(x, x, -px), ey = __builtin_fma(y, y, -py), ez = __builtin_fma(z, z, -pz);
+    double       s, e1, e2;
+    two_sum(px, py, s, e1);
+    two_sum(s, pz, hi, e2);
+    lo = ((ex + ey) + ez) + (e1 + e2);
+}
+template <typename T> __device__ __forceinline__ double ratio_sq(const typename Lane<T>::vec4& a, const typename Lane<T>::vec4& j) {
+    double q;
+    if constexpr (sizeof(T) == 4) {
+        const double ax = a.x, ay = a.y, az = a.z, jx = j.x, jy = j.y, jz = j.z;
+        const double a2 = ax * ax + ay * ay + az * az, j2 = jx * jx + jy * jy + jz * jz;
+        if (!(j2 > 0)) return __builtin_inf();
+        q = a2 / j2;
+    } else {
+        double ah, al, jh, jl;
+        norm2_pair(a.x, a.y, a.z, ah, al);
+        norm2_pair(j.x, j.y, j.z, jh, jl);
+        if (!(jh > 0)) return __builtin_inf();
+        q              = ah / jh;
+        const double r = __builtin_fma(-q, jh, ah) + (al - q * jl);
+        const double c = q + r / jh;
+        if (c == c && c - c == 0) q = c;
+    }
+    return (q == q && q - q == 0) ? q : __builtin_inf();  // (non-finite ratios are left out)
+}
+
+__device__ __forceinline__ double block_min(double m, double* lds) {
+    const int tid = threadIdx.x;
+    lds[tid]      = m;
+    __syncthreads();
+#pragma unroll 1
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) lds[tid] = fmin(lds[tid], lds[tid + half]);
+        __syncthreads();
+    }
+    return lds[0];
+}
+
+template <typename T> __global__ __launch_bounds__(256) void hermite_timestep_partial(const T* acc, const T* jerk, unsigned n, double* partial) {
+    using vec4 = typename Lane<T>::vec4;
+    __shared__ double lds[256];
+    double            m = __builtin_inf();
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256u) {
+        m = fmin(m, ratio_sq<T>(reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i]));
+    }
+    m = block_min(m, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+
+template <typename T> __global__ __launch_bounds__(256) void hermite_timestep_final(const double* partial, unsigned count, T eta, T* dt_out) {
+    __shared__ double lds[256];
+    double            m = __builtin_inf();
+    for (unsigned i = threadIdx.x; i < count; i += 256u) m = fmin(m, partial[i]);
+    m = block_min(m, lds);
+    if (threadIdx.x == 0) dt_out[0] = eta * static_cast<T>(__builtin_sqrt(m));
+}
+
+template <typename T, int S, bool STEP> hipError_t launch_s(const HermiteArgs<T>& a, const HermitePlan& p, hipStream_t stream) {
+    (void)hipGetLastError();  // a launch reports ITS OWN error
+    hipLaunchKernelGGL((hermite_eval<T, S, STEP>), dim3(p.groups), dim3(64 * S), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T, bool STEP> hipError_t launch_planned(const HermiteArgs<T>& a, hipStream_t stream) {
+    const HermitePlan p = plan_hermite<T>(a.n);
+    switch (p.waves) {
+        case 1: return launch_s<T, 1, STEP>(a, p, stream);
+        case 2: return launch_s<T, 2, STEP>(a, p, stream);
+        case 4: return launch_s<T, 4, STEP>(a, p, stream);
+        case 8: return launch_s<T, 8, STEP>(a, p, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+// Geometry, a function of (N, precision) alone.  One vector of bodies i per lane (I = W: 12 state vectors, 6 second-level sums and two
+// chains of 9 temporaries compile to 103 - 118 VGPRs; a second vector does not fit under 128), so a workgroup owns 64 W bodies i.  S, the waves that split j, is
+// the largest power of two up to 8 that still gives every wave a whole chunk of 128 bodies j: from 65 536 bodies (fp32; 32 768
+// fp64) the grid alone puts 16 waves on every CU of the MI355X.
+template <typename T> HermitePlan plan_hermite(unsigned n) {
+    constexpr int W = Lane<T>::W;
+    int           S = 1;
+    while (S < 8 && static_cast<unsigned>(2 * S) * kChunk <= n) S *= 2;
+    HermitePlan p;
+    p.bodies_per_lane = W;
+    p.waves           = S;
+    p.unroll          = unroll_for<T>();
+    p.groups          = (n + 64u * W - 1) / (64u * W);
+    p.block_threads   = 64u * S;
+    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * W * 64 * sizeof(T));
+    return p;
+}
+
+template <typename T> hipError_t launch_hermite_eval(const HermiteArgs<T>& a, hipStream_t stream) { return launch_planned<T, false>(a, stream); }
+
+template <typename T> hipError_t launch_hermite_step(const HermiteArgs<T>& a, T* workspace, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((hermite_predict<T>), dim3((a.n + 255u) / 256u), dim3(256), 0, stream, a.old_pos, static_cast<const T*>(a.vel), static_cast<const T*>(a.acc),
+                       static_cast<const T*>(a.jerk), workspace, a.n, a.dt);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    return launch_planned<T, true>(a, stream);
+}
+
+template <typename T> hipError_t launch_hermite_timestep(const T* acc, const T* jerk, unsigned n, T eta, T* dt_out, double* scratch, hipStream_t stream) {
+    const unsigned blocks = (n + 255u) / 256u < kTimestepPartials ? (n + 255u) / 256u : kTimestepPartials;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((hermite_timestep_partial<T>), dim3(blocks), dim3(256), 0, stream, acc, jerk, n, scratch);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL((hermite_timestep_final<T>), dim3(1), dim3(256), 0, stream, static_cast<const double*>(scratch), blocks, eta, dt_out);
+    return hipGetLastError();
+}
+
+template HermitePlan plan_hermite<float>(unsigned);
+template HermitePlan plan_hermite<double>(unsigned);
+template hipError_t  launch_hermite_eval<float>(const HermiteArgs<float>&, hipStream_t);
+template hipError_t  launch_hermite_eval<double>(const HermiteArgs<double>&, hipStream_t);
+template hipError_t  launch_hermite_step<float>(const HermiteArgs<float>&, float*, hipStream_t);
+template hipError_t  launch_hermite_step<double>(const HermiteArgs<double>&, double*, hipStream_t);
+template hipError_t  launch_hermite_timestep<float>(const float*, const float*, unsigned, float, float*, double*, hipStream_t);
+template hipError_t  launch_hermite_timestep<double>(const double*, const double*, unsigned, double, double*, double*, hipStream_t);
+
+}  // namespace nb

@@ -1,0 +1,109 @@
+// hermite_cli.cpp -- `nbody --integrator=hermite` (hermite_cli.hpp)
+#include "hermite_cli.hpp"
+
+#include "bodysystemhip_hermite.hpp"
+#include "compute.hpp"
+#include "randomise_bodies.hpp"
+#include "text.hpp"
+
+#include <cmath>
+#include <cstdio>
+#include <fstream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace {
+
+// nb_energy_* of the product library on the system's arrays (softening^2 is that library's process-global setting)
+template <typename T> auto energy_of(const BodySystemHIPHermite<T>& system, T softening_sq) -> nb_energy_t {
+    const auto  n     = static_cast<unsigned>(system.num_bodies());
+    std::size_t bytes = 0;
+    hip_check(nb_energy_workspace_bytes(n, &bytes), "nb_energy_workspace_bytes");
+    auto workspace = DeviceArray<unsigned char>(bytes);
+    auto result    = DeviceArray<nb_energy_t>(1);
+    if constexpr (sizeof(T) == 4) {
+        hip_check(nb_set_softening_sq_f32(softening_sq), "nb_set_softening_sq_f32");
+        hip_check(nb_energy_f32(system.positions(), system.velocities(), n, workspace.data(), bytes, result.data(), nullptr), "nb_energy_f32");
+    } else {
+        hip_check(nb_set_softening_sq_f64(softening_sq), "nb_set_softening_sq_f64");
+        hip_check(nb_energy_f64(system.positions(), system.velocities(), n, workspace.data(), bytes, result.data(), nullptr), "nb_energy_f64");
+    }
+    nb_energy_t out{};
+    result.download(std::span<nb_energy_t>(&out, 1));
+    return out;
+}
+
+auto print_energy(const std::string& what, const nb_energy_t& e) -> void {
+    std::printf("%s: kinetic=%.9g potential=%.9g total=%.9g momentum=%.9g,%.9g,%.9g", what.c_str(), e.kinetic, e.potential, e.total, e.momentum[0], e.momentum[1], e.momentum[2]);
+}
+
+template <typename T> auto run_typed(const HermiteRun& run) -> void {
+    const auto     n = run.num_bodies;
+    std::vector<T> pos(4 * n), vel(4 * n);
+    {
+        // the single-system start-up state (Compute's constructor): an fp32 and an fp64 system reset with demo row 0's scales, then
+        // the active precision with the N-scaled ones
+        std::vector<float>  p32(4 * n), v32(4 * n);
+        std::vector<double> p64(4 * n), v64(4 * n);
+        const auto demo0 = Compute::demo_params[0];
+        randomise_bodies<float>(NBodyConfig::NBODY_CONFIG_SHELL, p32, v32, demo0.cluster_scale, demo0.velocity_scale);
+        randomise_bodies<double>(NBodyConfig::NBODY_CONFIG_SHELL, p64, v64, demo0.cluster_scale, demo0.velocity_scale);
+        auto scaled = demo0;
+        Compute::scale_params_for(n, scaled);
+        randomise_bodies<T>(run.config, pos, vel, scaled.cluster_scale, scaled.velocity_scale);
+    }
+    // BodySystemHIP's conversions: dt float -> T, softening^2 = T(s) * T(s)
+    const T dt = static_cast<T>(run.params.time_step);
+    const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
+    auto system = BodySystemHIPHermite<T>(n, softening_sq);
+    system.set_state(pos, vel);
+    const auto measure = run.energy && (run.benchmark || run.steps > 0);
+    nb_energy_t start{};
+    if (measure) start = energy_of(system, softening_sq);
+    const auto report_energy = [&](std::size_t steps) {
+        if (!measure) return;
+        const auto end = energy_of(system, softening_sq);
+        print_energy("energy start", start);
+        std::printf("\n");
+        print_energy("energy end (" + std::to_string(steps) + " steps)", end);
+        std::printf(" relative_drift=%.9g\n", (end.total - start.total) / std::abs(start.total));
+    };
+    if (run.benchmark) {
+        system.update(dt);  // (untimed, as Compute::run_benchmark)
+        HipEvent begin, stop;
+        begin.record();
+        for (int i = 0; i < run.iterations; ++i) system.update(dt);
+        stop.record();
+        stop.synchronize();
+        const float milliseconds = HipEvent::elapsed_ms(begin, stop);
+        const float frequency    = static_cast<float>(run.iterations) * (1000.0f / milliseconds);
+        const float interactions = static_cast<float>(static_cast<double>(n) * static_cast<double>(n) * 1e-9) * frequency;
+        // an acceleration + jerk interaction as this library evaluates it: 3 + 3 subtractions, 2 x 5 for r.r + eps^2 and r.w, rsqrt (4,
+        // the reference's convention), 2 + 1 products for s^-2, s^-3 and the mass, 2 for -3 (r.w) s^-2, 6 + 12 for the two sums
+        const int flops = 43;
+        std::printf("%zu bodies, hermite integrator, total time for %d iterations: %s ms\n", n, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("= %s ms per step\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
+        std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
+        std::printf("= %s %s-precision GFLOP/s at %d flops per acceleration + jerk interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
+                    sizeof(T) == 8 ? "double" : "single", flops);
+        report_energy(1 + static_cast<std::size_t>(run.iterations));
+        return;
+    }
+    for (std::size_t s = 0; s < run.steps; ++s) system.update(dt);
+    if (!run.dump.empty()) {
+        system.get_positions(pos);
+        system.get_velocities(vel);
+        auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
+        if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
+        out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
+        out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
+    }
+    report_energy(run.steps);
+}
+
+}  // namespace
+
+auto run_hermite(const HermiteRun& run) -> void {
+    if (run.fp64) run_typed<double>(run); else run_typed<float>(run);
+}

@@ -1,0 +1,23 @@
+// hermite_cli.hpp -- `nbody --integrator=hermite`: the single-system run stepped by the 4th-order Hermite scheme (BodySystemHIPHermite).
+#pragma once
+
+#include "nbody_types.hpp"
+
+#include <cstddef>
+#include <filesystem>
+
+struct HermiteRun {
+    bool                  fp64 = false;
+    std::size_t           num_bodies = 0;
+    NBodyConfig           config = NBodyConfig::NBODY_CONFIG_SHELL;
+    NBodyParams           params{};  // the demo row (dt, softening; its damping is not used: the scheme has none)
+    bool                  benchmark = false;
+    int                   iterations = 10;
+    std::size_t           steps = 0;
+    std::filesystem::path dump;
+    bool                  energy = false;
+};
+
+// Starts from the current rand() state (main has applied --seed) with the single-system start-up state (the same three
+// randomise_bodies segments as Compute's constructor).  --benchmark: one untimed step, then `iterations` timed ones.
+auto run_hermite(const HermiteRun& run) -> void;

@@ -8,7 +8,10 @@
 //                     --mode=fast|strict  --config=shell|random|expand  --demo=<0..6>  --steps=<n>  --dump=<file>
 //                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
+//                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 #include "ensemble_cli.hpp"
+#include "hermite_cli.hpp"
+#include "../../include/nbody_hip_hermite.h"
 #include "compute.hpp"
 #include "integrate_nbody_hip.hpp"
 
@@ -61,6 +64,7 @@ struct Options {
     std::optional<std::size_t> demo;   // row of Compute::demo_params (the reference reaches them from the viewer's keys only)
     double                inject_error = 0.0;
     std::size_t           systems = 0;  // --systems=<B>: an ensemble of B systems (0: one system, the reference's run)
+    bool                  hermite = false;  // --integrator=hermite (euler, the reference's step, is the default)
 };
 
 constexpr auto help_text = R"(The MI355X NBody hot path (drop-in for cuda-nbody's compute path).
@@ -99,6 +103,9 @@ Options:
   --systems UINT              Step this many independent systems of --numbodies (<= 65536, required) bodies in one launch: system 0
                               is the single-system start-up state, the others the next draws; --benchmark counts B*N^2 interactions
                               per step, --dump writes every system's positions, then every system's velocities
+  --integrator TEXT [euler]   euler | hermite.  hermite: 4th-order Hermite predictor-corrector steps (acceleration and jerk per
+                              interaction, no damping) of --numbodies (required) bodies on one device, FAST arithmetic; with
+                              --benchmark, --steps, --dump and --energy
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
 
@@ -236,6 +243,10 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             const auto v = take_value();
             ok           = v && (*v == "fast" || *v == "strict");
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
+        } else if (name == "integrator") {
+            const auto v = take_value();
+            ok           = v && (*v == "euler" || *v == "hermite");
+            if (ok) options.hermite = *v == "hermite";
         } else if (name == "config") {
             const auto v = take_value();
             ok           = v && (*v == "shell" || *v == "random" || *v == "expand");
@@ -257,6 +268,17 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         if (options.devices.size() > 1) return error("--systems is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
         if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.energy || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
             return error("--systems cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --energy, --no-workspace, --workspace-mib or --cpu");
+        }
+    }
+
+    if (options.hermite) {
+        if (options.numbodies == 0) return error("--integrator=hermite needs an explicit --numbodies");
+        if (options.numbodies > NB_HERMITE_MAX_BODIES) return error("--integrator=hermite: --numbodies must be at most 67108864");
+        if (options.mode == NB_MODE_STRICT) return error("--integrator=hermite has no strict mode: there is no CPU reference arithmetic to reproduce");
+        if (options.devices.size() > 1) return error("--integrator=hermite is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
+        if (options.systems > 0) return error("--integrator=hermite cannot be combined with --systems");
+        if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
+            return error("--integrator=hermite cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --no-workspace, --workspace-mib or --cpu");
         }
     }
 
@@ -314,6 +336,22 @@ auto main(int argc, char** argv) -> int {
             run.steps       = cmd_options.steps;
             run.dump        = cmd_options.dump;
             run_ensemble(run);
+            return 0;
+        }
+
+        if (cmd_options.hermite) {
+            if (!cmd_options.benchmark && cmd_options.steps == 0 && cmd_options.dump.empty()) throw std::invalid_argument("--integrator=hermite: pass --benchmark or --steps/--dump");
+            auto run       = HermiteRun{};
+            run.fp64       = cmd_options.fp64;
+            run.num_bodies = cmd_options.numbodies;
+            run.config     = cmd_options.config;
+            run.params     = Compute::demo_params[cmd_options.demo.value_or(0)];
+            run.benchmark  = cmd_options.benchmark;
+            run.iterations = cmd_options.iterations == 0 ? 10 : static_cast<int>(cmd_options.iterations);
+            run.steps      = cmd_options.steps;
+            run.dump       = cmd_options.dump;
+            run.energy     = cmd_options.energy;
+            run_hermite(run);
             return 0;
         }
 
