@@ -30,6 +30,8 @@ LAB_LIB_PATH = os.environ.get("NBODY_HIP_LAB_LIB", os.path.join(HERE, "libnbody_
 ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_ensemble.so"))
 # 4th-order Hermite steps (include/nbody_hip_hermite.h) are a fourth library on the same terms, loaded by hermite_lib().
 HERMITE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_LIB", os.path.join(HERE, "libnbody_hip_hermite.so"))
+# Hermite steps with block time steps (include/nbody_hip_hermite_block.h) are a fifth, loaded by hermite_block_lib().
+HERMITE_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_LIB", os.path.join(HERE, "libnbody_hip_hermite_block.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -253,9 +255,46 @@ HERMITE_SIGNATURES = {
     "nb_hermite_timestep_f64": (_ci, [_vp, _vp, _cu, _cd, _vp, _vp, _sz, _vp]),
 }
 
+
+# include/nbody_hip_hermite_block.h: exported by libnbody_hip_hermite_block.so, and nothing else is
+class HermiteBlockParams(ctypes.Structure):
+    """nb_hermite_block_params_t"""
+    _fields_ = [("eta", _cd), ("eta_start", _cd), ("dt_max", _cd), ("max_level", _ci), ("reserved", _ci)]
+
+
+class HermiteBlockStatus(ctypes.Structure):
+    """nb_hermite_block_status_t: 64 bytes of device memory the block steps keep up to date"""
+    _fields_ = [("now_ticks", ctypes.c_uint64), ("block_steps", ctypes.c_uint64), ("body_steps", ctypes.c_uint64), ("last_active", ctypes.c_uint32),
+                ("deepest_level", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+class HermiteBlockPlan(ctypes.Structure):
+    """nb_hermite_block_plan_t: the geometry of one block step's evaluation, a function of N, n_act and the precision"""
+    _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("unroll", _ci), ("tiles", _cu), ("ranges", _cu), ("groups", _cu),
+                ("launch_groups", _cu), ("block_threads", _cu), ("lds_bytes", _cu), ("slots", _cu), ("chunks", _cu), ("launches", _cu),
+                ("partial_offset", ctypes.c_ulonglong), ("partial_bytes", ctypes.c_ulonglong)]
+
+
+HERMITE_BLOCK_MAX_BODIES = 1 << 24
+HERMITE_BLOCK_MAX_LEVEL = 40
+HERMITE_BLOCK_STOPPED = 1
+_block_state = [_vp] * 8 + [_sz, _cu]  # positions velocities accelerations jerks ticks levels status workspace, workspace_bytes, N
+HERMITE_BLOCK_SIGNATURES = {
+    "nb_hermite_block_workspace_bytes": (_ci, [_cu, _cu, _P(_sz)]),
+    "nb_hermite_block_plan_f32": (_ci, [_cu, _cu, _P(HermiteBlockPlan)]),
+    "nb_hermite_block_plan_f64": (_ci, [_cu, _cu, _P(HermiteBlockPlan)]),
+    "nb_hermite_block_init_f32": (_ci, _block_state + [_cf, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_init_f64": (_ci, _block_state + [_cd, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_step_f32": (_ci, _block_state + [_cf, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite_block_step_f64": (_ci, _block_state + [_cd, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite_block_sync_f32": (_ci, [_vp] * 8 + [_cu, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_sync_f64": (_ci, [_vp] * 8 + [_cu, _P(HermiteBlockParams), _vp]),
+}
+
 _lib = None
 _ensemble_lib = None
 _hermite_lib = None
+_hermite_block_lib = None
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
 
 
@@ -316,6 +355,21 @@ def hermite_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _hermite_lib = handle
     return _hermite_lib
+
+
+def hermite_block_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite_block.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _hermite_block_lib
+    if _hermite_block_lib is None:
+        if not os.path.exists(HERMITE_BLOCK_LIB_PATH):
+            raise FileNotFoundError(f"{HERMITE_BLOCK_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(HERMITE_BLOCK_LIB_PATH)
+        for name, (restype, argtypes) in HERMITE_BLOCK_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _hermite_block_lib = handle
+    return _hermite_block_lib
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -698,6 +752,130 @@ class HermiteSystem:
 
     def get_jerks(self) -> np.ndarray:
         return self._download(self._jerk)
+
+    def synchronize(self) -> None:
+        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+def hermite_block_plan(num_bodies: int, num_active: int, dtype=np.float32) -> HermiteBlockPlan:
+    """nb_hermite_block_plan_*: the geometry of a block step of `num_active` of `num_bodies` bodies"""
+    p = HermiteBlockPlan()
+    fn = hermite_block_lib().nb_hermite_block_plan_f32 if np.dtype(dtype) == np.float32 else hermite_block_lib().nb_hermite_block_plan_f64
+    check(fn(num_bodies, num_active, ctypes.byref(p)), "nb_hermite_block_plan")
+    return p
+
+
+def hermite_block_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(hermite_block_lib().nb_hermite_block_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_hermite_block_workspace_bytes")
+    return out.value
+
+
+class HermiteBlockSystem:
+    """One system of N bodies on the device, stepped by the Hermite scheme with block time steps of include/nbody_hip_hermite_block.h.
+
+    The state (positions, velocities, accelerations, jerks, ticks, levels), the status record and the workspace are owned here.
+    ``set_state`` uploads (N, 4) positions {x, y, z, m} and velocities; ``init`` evaluates and assigns the first levels; ``step(t_stop)``
+    enqueues one block step; ``advance(t_stop, batch)`` enqueues batches of block steps and reads the status between them until a
+    step would pass t_stop; ``snapshot()`` is the synchronised state at the status time; ``status()`` the status record."""
+
+    def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None, eta=0.02, eta_start=0.01, dt_max=0.125, max_level=30):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies = int(num_bodies)
+        t = self.dtype.type
+        self.softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else t(softening_sq)
+        self.params = HermiteBlockParams(float(eta), float(eta_start), float(dt_max), int(max_level), 0)
+        self.tick = float(dt_max) * 2.0 ** -int(max_level)
+        self._workspace_bytes = hermite_block_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
+        self.shape = (self.num_bodies, 4)
+        nbytes = 4 * self.num_bodies * self.dtype.itemsize
+        self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out = (DeviceBuffer(nbytes) for _ in range(6))
+        self._ticks, self._levels = DeviceBuffer(8 * self.num_bodies), DeviceBuffer(4 * self.num_bodies)
+        self._status = DeviceBuffer(ctypes.sizeof(HermiteBlockStatus))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+
+    def _buffers(self):
+        return [self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out, self._ticks, self._levels, self._status, self._workspace]
+
+    def _state_args(self):
+        return (self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._levels.ptr, self._status.ptr, self._workspace.ptr,
+                self._workspace_bytes, self.num_bodies, self._scalar(self.softening_sq), ctypes.byref(self.params))
+
+    def set_state(self, positions, velocities) -> None:
+        for buf, data in ((self._pos, positions), (self._vel, velocities)):
+            data = np.ascontiguousarray(data, dtype=self.dtype)
+            if data.shape != self.shape:
+                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
+            buf.upload(data)
+
+    def init(self, stream=None) -> None:
+        fn = getattr(hermite_block_lib(), "nb_hermite_block_init_" + self._suffix)
+        check(fn(*self._state_args(), stream), "nb_hermite_block_init")
+
+    def step(self, t_stop=float("inf"), stream=None) -> None:
+        fn = getattr(hermite_block_lib(), "nb_hermite_block_step_" + self._suffix)
+        check(fn(*self._state_args(), float(t_stop), stream), "nb_hermite_block_step")
+
+    def status(self, stream=None) -> HermiteBlockStatus:
+        out = HermiteBlockStatus()
+        check(lib().nb_d2h(ctypes.byref(out), self._status.ptr, ctypes.sizeof(out), stream), "nb_d2h(status)")
+        return out
+
+    def time(self) -> float:
+        return self.status().now_ticks * self.tick
+
+    def advance(self, t_stop, batch: int = 64, stream=None) -> HermiteBlockStatus:
+        """block steps until the next one would pass t_stop: `batch` calls are enqueued, then the status is read"""
+        while True:
+            for _ in range(batch):
+                self.step(t_stop, stream)
+            status = self.status(stream)
+            if status.flags & HERMITE_BLOCK_STOPPED:
+                return status
+
+    def snapshot(self, stream=None):
+        """(positions, velocities) of every body predicted to the status time (nb_hermite_block_sync_*)"""
+        self.sync(stream)
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+        return self._download(self._pos_out), self._download(self._vel_out)
+
+    def sync(self, stream=None) -> None:
+        """the synchronised snapshot, left on the device: snapshot_ptrs() for nb_energy_*"""
+        fn = getattr(hermite_block_lib(), "nb_hermite_block_sync_" + self._suffix)
+        check(fn(self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._status.ptr,
+                 self.num_bodies, ctypes.byref(self.params), stream), "nb_hermite_block_sync")
+
+    def snapshot_ptrs(self):
+        return self._pos_out.ptr, self._vel_out.ptr
+
+    def _download(self, buf: DeviceBuffer) -> np.ndarray:
+        return buf.download(np.empty(self.shape, dtype=self.dtype))
+
+    def get_positions(self) -> np.ndarray:
+        return self._download(self._pos)
+
+    def get_velocities(self) -> np.ndarray:
+        return self._download(self._vel)
+
+    def get_accelerations(self) -> np.ndarray:
+        return self._download(self._acc)
+
+    def get_jerks(self) -> np.ndarray:
+        return self._download(self._jerk)
+
+    def get_ticks(self) -> np.ndarray:
+        return self._ticks.download(np.empty(self.num_bodies, dtype=np.uint64))
+
+    def get_levels(self) -> np.ndarray:
+        return self._levels.download(np.empty(self.num_bodies, dtype=np.int32))
 
     def synchronize(self) -> None:
         check(lib().nb_device_synchronize(), "nb_device_synchronize")

@@ -1,0 +1,534 @@
+// hermite_block.hip -- the kernels of libnbody_hip_hermite_block.so (include/nbody_hip_hermite_block.h): 4th-order Hermite steps with
+// block time steps.  gfx950 only; FMA contraction on.
+//
+// One block step is six launches, no atomics, every word written by one lane:
+//   block_min_partial    per workgroup, the minimum of tick + ticks(level) (and the deepest level held)
+//   block_predict_count  every workgroup folds those partials (<= 1 024) to `now`; workgroup 0 records it, decides about t_stop and
+//                        writes the flag; every body is predicted to `now` into the workspace; active bodies are counted per workgroup
+//   block_scan           ONE workgroup: exclusive prefix of the counts in index order, n_act, the status counters
+//   block_scatter        the active list, ascending body index
+//   hermite_block_eval   the hot path, see below
+//   hermite_block_finish one lane per active slot: J partials in index order, corrector, dt_A, new level, the body's stored state
+// A step that would pass t_stop leaves go = 0 in the control record and the four launches after it return at once.
+//
+// hermite_block_eval<T, S> has hermite_eval's streaming loops (the text of hermite_stream.inc: bodies j by scalar loads U at a time into two
+// register sets, unit / mixed forms, two-level sums, SIMD-mate priority; 25 / 26 v_pk_* + 2 v_rsq_f32 per packed pair, no LDS, barrier
+// or scratch inside them) around another distribution of work: a workgroup owns one tile of 64 W ACTIVE bodies, gathered through the
+// active list from the predicted state, and one of J contiguous ranges of the chunks of bodies j.  Its S waves split the range's
+// chunks (chunk c of the range -> wave c mod S), fold through LDS in wave order, and wave 0 stores six partial sums per body, in units
+// of the reference mass, to the planes [J][6][tiles 64 W].  (tile, range) come from n_act, which the workgroup reads from the control
+// record: the launch grid is sized for the worst n_act of this N and the workgroups beyond tiles J leave.
+#include "hermite_block_kernels.h"
+
+namespace nb {
+namespace {
+
+#include "nbody_lane.h"
+
+#include "hermite_stream.h"
+static_assert(kChunk == static_cast<int>(kBlockChunk), "the geometry counts hermite_stream.h's chunks");
+
+__device__ __forceinline__ unsigned long long ticks_of(int level, int max_level) {
+    const int k = level < 0 ? 0 : (level > max_level ? max_level : level);
+    return 1ull << (max_level - k);
+}
+__device__ __forceinline__ double tick_length(const BlockParams& p) { return __builtin_ldexp(p.dt_max, -p.max_level); }
+
+template <typename T, int S>
+__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_block_eval(const T* state8, const unsigned* active, const BlockCtrl* ctrl, T* partial,
+                                                                                                       unsigned n, T eps2_in) {
+    using LT         = Lane<T>;
+    using vec4       = typename LT::vec4;
+    using vec        = typename LT::vec;
+    using raw4       = typename LT::raw4;
+    using bits       = typename LT::bits;
+    constexpr int W  = LT::W;  // bodies i per lane
+    constexpr int U  = unroll_for<T>();
+    constexpr int CH = kChunk;
+    constexpr int LPT = CH / 64;
+    static_assert(CH % U == 0, "the streaming loop is unrolled by U");
+    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx8 / x16
+
+    if (ctrl->go == 0) return;
+    const unsigned  n_act = ctrl->n_act;
+    const BlockGeom geom  = block_geometry(n, n_act, 64 * W);
+    if (blockIdx.x >= geom.tiles * geom.ranges) return;
+    const unsigned tile  = blockIdx.x / geom.ranges;
+    const unsigned range = blockIdx.x % geom.ranges;
+    const unsigned slots = geom.tiles * (64 * W);
+
+    const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state8));
+    const int        tid  = threadIdx.x;
+    const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int        lane = tid & 63;
+
+    // bodies i of this lane: slots tile_base + k*64 + lane of the active list
+    const unsigned tile_base = tile * (64 * W);
+    vec            px, py, pz, vx, vy, vz;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned slot = tile_base + k * 64 + lane;
+        const size_t   i    = active[slot < n_act ? slot : n_act - 1];
+        const vec4     p    = reinterpret_cast<const vec4*>(state8)[2 * i];
+        const vec4     v    = reinterpret_cast<const vec4*>(state8)[2 * i + 1];
+        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
+        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
+    }
+    const T    m_first   = jp[0].w;  // (a scalar load)
+    const T    m_ref     = usable_unit(m_first) ? m_first : T(1);
+    const T    inv_mref  = T(1) / m_ref;
+    const bits unit_bits = __builtin_bit_cast(bits, m_ref);
+    vec        eps2      = LT::splat(eps2_in);
+    LT::keep_in_vgpr(eps2);
+    const vec                 minus3 = LT::splat(T(-3));
+    const typename LT::Consts consts = LT::make_consts();
+
+    vec first[6], second[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) first[q] = second[q] = LT::splat(0);
+
+    // the range's chunks: [c_lo, c_hi), never empty (J <= n_chunks / S)
+    const unsigned n_chunks = block_chunks(n);
+    const unsigned c_lo     = static_cast<unsigned>(static_cast<unsigned long long>(range) * n_chunks / geom.ranges);
+    const unsigned c_hi     = static_cast<unsigned>(static_cast<unsigned long long>(range + 1) * n_chunks / geom.ranges);
+
+    auto chunk_is_unit = [&](unsigned c) -> bool {
+        const unsigned first_j = c * CH;
+        bool           same    = n - first_j >= static_cast<unsigned>(CH) || (n - first_j) % U == 0;
+#pragma unroll
+        for (int r = 0; r < LPT; ++r) {
+            const unsigned j = first_j + r * 64 + lane;
+            same             = same && (j >= n || __builtin_bit_cast(bits, state8[8 * static_cast<size_t>(j < n ? j : first_j) + 3]) == unit_bits);
+        }
+        return __builtin_amdgcn_ballot_w64(!same) == 0;
+    };
+    auto group = [&](size_t j0, BodyJ<T> (&b)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) b[u].p = jp[2 * (j0 + u)], b[u].v = jp[2 * (j0 + u) + 1];  // adjacent: one s_load_dwordx8 / x16
+    };
+#include "hermite_stream.inc"
+
+    // SIMD-mate priority, as hermite_eval (plain LDS words, one writer each; no result bit depends on it)
+    __shared__ unsigned progress[4 * 8];
+    if (tid < 32) progress[tid] = 0xffffffffu;
+    __syncthreads();
+    const unsigned           simd = static_cast<unsigned>(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4));  // HW_REG_HW_ID[5:4] = SIMD_ID
+    volatile unsigned* const mine = progress + simd * 8;
+    unsigned                 done = 0;
+    if (lane == 0) mine[wave] = 0;
+
+    unsigned c       = c_lo + wave;  // wave w streams chunks c_lo + w, c_lo + w + S, ...
+    bool     unit    = c < c_hi ? chunk_is_unit(c) : false;
+    bool     is_unit = true;
+    unsigned held    = 0;
+    BodyJ<T> b0[U], b1[U];
+    if (c < c_hi && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
+    for (; c < c_hi; c += S) {
+        const bool next_unit = (c + S) < c_hi ? chunk_is_unit(c + S) : false;
+        if constexpr (S > 1) {
+            unsigned least = done;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) least = min(least, mine[q]);
+            if (static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(least))) >= done) {
+                __builtin_amdgcn_s_setprio(3);
+            } else {
+                __builtin_amdgcn_s_setprio(0);
+            }
+        }
+        const unsigned first_j = c * CH;
+        const unsigned count   = min(static_cast<unsigned>(CH), n - first_j);
+        const unsigned groups  = count / U;
+        const size_t   next    = ((c + S) < c_hi && n - (first_j + S * CH) >= static_cast<unsigned>(U)) ? static_cast<size_t>(first_j) + S * CH : first_j;
+        if (unit != is_unit || held == kFlushEvery) {
+            flush();
+            is_unit = unit, pending_scale = unit ? T(1) : inv_mref, held = 0;
+        }
+        if (groups > 0) {
+            if (unit) {
+                stream.template operator()<true>(first_j, groups, next, b0, b1);
+            } else {
+                stream.template operator()<false>(first_j, groups, next, b0, b1);
+            }
+        }
+#pragma unroll 1
+        for (unsigned jj = groups * U; jj < count; ++jj) {  // ragged end of the last chunk (mixed)
+            BodyJ<T> one[1];
+            one[0].p = jp[2 * (static_cast<size_t>(first_j) + jj)], one[0].v = jp[2 * (static_cast<size_t>(first_j) + jj) + 1];
+            compute.template operator()<false, 1>(one, first);
+        }
+        ++held;
+        unit = next_unit;
+        ++done;
+        if (lane == 0) mine[wave] = done;
+    }
+    if (lane == 0) mine[wave] = 0xffffffffu;
+    __builtin_amdgcn_s_setprio(0);
+    flush();
+
+    // fold the S partial sums (waves 1..S-1 -> wave 0) through LDS, fixed order
+    __shared__ T red[(S > 1 ? S - 1 : 1) * 6 * W * 64];
+    if (wave > 0) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) red[(((wave - 1) * 6 + q) * W + k) * 64 + lane] = LT::get(second[q], k);
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+#pragma unroll 1
+    for (int g = 1; g < S; ++g) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) LT::set(second[q], k, LT::get(second[q], k) + red[(((g - 1) * 6 + q) * W + k) * 64 + lane]);
+        }
+    }
+    // planes [J][6][slots]: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) partial[(static_cast<size_t>(range) * 6 + q) * slots + tile_base + k * 64 + lane] = LT::get(second[q], k);
+    }
+}
+
+// ---- the schedule ---------------------------------------------------------------------------------------------------------------------
+
+struct MinLevel {
+    unsigned long long next;
+    int                level;
+};
+// the minimum of `next` and the maximum of `level` over a workgroup of 256
+__device__ __forceinline__ MinLevel block_fold(MinLevel m, unsigned long long* lds_next, int* lds_level) {
+    const int tid  = threadIdx.x;
+    lds_next[tid]  = m.next;
+    lds_level[tid] = m.level;
+    __syncthreads();
+#pragma unroll 1
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) {
+            const unsigned long long other = lds_next[tid + half];
+            if (other < lds_next[tid]) lds_next[tid] = other;
+            const int deeper = lds_level[tid + half];
+            if (deeper > lds_level[tid]) lds_level[tid] = deeper;
+        }
+        __syncthreads();
+    }
+    return MinLevel{lds_next[0], lds_level[0]};
+}
+
+__global__ __launch_bounds__(256) void block_min_partial(const unsigned long long* ticks, const int* levels, unsigned n, int max_level, unsigned long long* min_part, int* lvl_part) {
+    __shared__ unsigned long long lds_next[256];
+    __shared__ int                lds_level[256];
+    MinLevel                      m{~0ull, 0};
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256u) {
+        const int                k    = levels[i];
+        const unsigned long long next = ticks[i] + ticks_of(k, max_level);
+        if (next < m.next) m.next = next;
+        if (k > m.level) m.level = k;
+    }
+    m = block_fold(m, lds_next, lds_level);
+    if (threadIdx.x == 0) min_part[blockIdx.x] = m.next, lvl_part[blockIdx.x] = m.level;
+}
+
+// the predictor of nb_hermite_step_* (hermite_predict) for one body
+template <typename T> __device__ __forceinline__ void predict_body(const typename Lane<T>::vec4& x, const typename Lane<T>::vec4& v, const typename Lane<T>::vec4& a,
+                                                                 const typename Lane<T>::vec4& j, T dt, typename Lane<T>::vec4& xp, typename Lane<T>::vec4& vp) {
+    const T h = dt * T(0.5), t = dt * (T(1) / T(3));
+    xp.x = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.x, a.x), v.x), x.x);
+    xp.y = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.y, a.y), v.y), x.y);
+    xp.z = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.z, a.z), v.z), x.z);
+    xp.w = x.w;
+    vp.x = __builtin_fma(dt, __builtin_fma(h, j.x, a.x), v.x);
+    vp.y = __builtin_fma(dt, __builtin_fma(h, j.y, a.y), v.y);
+    vp.z = __builtin_fma(dt, __builtin_fma(h, j.z, a.z), v.z);
+    vp.w = 0;
+}
+
+template <typename T> __global__ __launch_bounds__(256) void block_predict_count(BlockArgs<T> a, unsigned partials) {
+    using vec4 = typename Lane<T>::vec4;
+    __shared__ unsigned long long lds_next[256];
+    __shared__ int                lds_level[256];
+    __shared__ unsigned           wave_count[4];
+    MinLevel                      m{~0ull, 0};
+    for (unsigned i = threadIdx.x; i < partials; i += 256u) {
+        const unsigned long long next = a.min_part[i];
+        const int                k    = a.lvl_part[i];
+        if (next < m.next) m.next = next;
+        if (k > m.level) m.level = k;
+    }
+    m                            = block_fold(m, lds_next, lds_level);
+    const unsigned long long now = m.next;
+    const double             q   = tick_length(a.p);
+    const bool               go  = static_cast<double>(now) * q <= a.t_stop;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.ctrl->now = now, a.ctrl->go = go ? 1u : 0u;
+        if (!go) a.ctrl->n_act = 0;
+        const unsigned flags    = a.status->flags;
+        a.status->flags         = go ? (flags & ~kBlockStopped) : (flags | kBlockStopped);
+        const int deepest       = a.status->deepest_level;
+        a.status->deepest_level = m.level > deepest ? m.level : deepest;
+    }
+    if (!go) return;
+    const unsigned i      = blockIdx.x * 256u + threadIdx.x;
+    bool           active = false;
+    if (i < a.n) {
+        const unsigned long long tick = a.ticks[i];
+        active                        = tick + ticks_of(a.levels[i], a.p.max_level) == now;
+        const T                  dt   = static_cast<T>(static_cast<double>(now - tick) * q);
+        const vec4 x = reinterpret_cast<const vec4*>(a.pos)[i], v = reinterpret_cast<const vec4*>(a.vel)[i];
+        const vec4 acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
+        vec4       xp, vp;
+        predict_body<T>(x, v, acc, jerk, dt, xp, vp);
+        reinterpret_cast<vec4*>(a.state8)[2 * static_cast<size_t>(i)]     = xp;
+        reinterpret_cast<vec4*>(a.state8)[2 * static_cast<size_t>(i) + 1] = vp;
+    }
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
+    __syncthreads();
+    if (threadIdx.x == 0) a.counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+}
+
+// counts[b] -> the number of active bodies in the workgroups before b (in place); n_act; the status counters.  One workgroup of 1 024.
+__global__ __launch_bounds__(1024) void block_scan(unsigned* counts, unsigned blocks, BlockCtrl* ctrl, BlockStatus* status) {
+    __shared__ unsigned sums[1024];
+    if (ctrl->go == 0) return;
+    const unsigned tid = threadIdx.x, per = (blocks + 1023u) / 1024u;
+    const unsigned lo = tid * per < blocks ? tid * per : blocks, hi = lo + per < blocks ? lo + per : blocks;
+    unsigned       mine = 0;
+    for (unsigned b = lo; b < hi; ++b) mine += counts[b];
+    sums[tid] = mine;
+    __syncthreads();
+#pragma unroll 1
+    for (unsigned step = 1; step < 1024u; step *= 2) {  // inclusive scan; integer sums, so the order changes nothing
+        const unsigned add = tid >= step ? sums[tid - step] : 0u;
+        __syncthreads();
+        sums[tid] += add;
+        __syncthreads();
+    }
+    unsigned before = sums[tid] - mine;
+    for (unsigned b = lo; b < hi; ++b) {
+        const unsigned count = counts[b];
+        counts[b]            = before;
+        before += count;
+    }
+    if (tid == 1023u) {
+        const unsigned n_act = sums[1023];
+        ctrl->n_act          = n_act;
+        status->now_ticks    = ctrl->now;
+        status->block_steps += 1;
+        status->body_steps += n_act;
+        status->last_active = n_act;
+    }
+}
+
+__global__ __launch_bounds__(256) void block_scatter(const unsigned long long* ticks, const int* levels, const unsigned* offsets, const BlockCtrl* ctrl, unsigned* active_list,
+                                                     unsigned n, int max_level) {
+    __shared__ unsigned wave_count[4];
+    if (ctrl->go == 0) return;
+    const unsigned long long now    = ctrl->now;
+    const unsigned           i      = blockIdx.x * 256u + threadIdx.x;
+    const bool               active = i < n && ticks[i] + ticks_of(levels[i], max_level) == now;
+    const unsigned long long mask   = __builtin_amdgcn_ballot_w64(active);
+    const unsigned           wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) wave_count[wave] = static_cast<unsigned>(__builtin_popcountll(mask));
+    __syncthreads();
+    if (!active) return;
+    unsigned at = offsets[blockIdx.x] + static_cast<unsigned>(__builtin_popcountll(mask & ((1ull << lane) - 1ull)));
+    for (unsigned w = 0; w < wave; ++w) at += wave_count[w];
+    active_list[at] = i;
+}
+
+__device__ __forceinline__ double norm3(double x, double y, double z) { return __builtin_sqrt(x * x + y * y + z * z); }
+
+// Aarseth's step from the stored T-typed a0, j0, a1, j1, in fp64 (include/nbody_hip_hermite_block.h)
+template <typename V> __device__ __forceinline__ double aarseth_dt(const V& a0, const V& j0, const V& a1, const V& j1, double h, double eta, double dt_max) {
+    const double d[3]  = {static_cast<double>(a0.x) - static_cast<double>(a1.x), static_cast<double>(a0.y) - static_cast<double>(a1.y), static_cast<double>(a0.z) - static_cast<double>(a1.z)};
+    const double p0[3] = {static_cast<double>(j0.x), static_cast<double>(j0.y), static_cast<double>(j0.z)};
+    const double p1[3] = {static_cast<double>(j1.x), static_cast<double>(j1.y), static_cast<double>(j1.z)};
+    double       a2e[3], a3[3];
+    const double h2 = h * h, h3 = h2 * h;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double a2 = (-6.0 * d[c] - h * (4.0 * p0[c] + 2.0 * p1[c])) / h2;
+        a3[c]           = (12.0 * d[c] + 6.0 * h * (p0[c] + p1[c])) / h3;
+        a2e[c]          = a2 + h * a3[c];
+    }
+    const double n_a1 = norm3(a1.x, a1.y, a1.z), n_j1 = norm3(p1[0], p1[1], p1[2]), n_a2 = norm3(a2e[0], a2e[1], a2e[2]), n_a3 = norm3(a3[0], a3[1], a3[2]);
+    const double dt = __builtin_sqrt(eta * (n_a1 * n_a2 + n_j1 * n_j1) / (n_j1 * n_a3 + n_a2 * n_a2));
+    return (dt == dt && dt - dt == 0) ? dt : dt_max;
+}
+
+template <typename T> __global__ __launch_bounds__(256) void hermite_block_finish(BlockArgs<T> a) {
+    using vec4 = typename Lane<T>::vec4;
+    constexpr unsigned per_tile = 64 * Lane<T>::W;
+    if (a.ctrl->go == 0) return;
+    const unsigned n_act = a.ctrl->n_act;
+    const unsigned slot  = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= n_act) return;
+    const BlockGeom          geom  = block_geometry(a.n, n_act, per_tile);
+    const size_t             slots = static_cast<size_t>(geom.tiles) * per_tile;
+    const unsigned long long now   = a.ctrl->now;
+    const size_t             i     = a.active[slot];
+    T                        sum[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) sum[q] = a.partial[q * slots + slot];
+    // the other ranges in index order, eight ranges' loads in flight at a time (one lane's J x 6 dependent round trips to L2 were a third
+    // of a block step with a handful of active bodies)
+#pragma unroll 1
+    for (unsigned r0 = 1; r0 < geom.ranges; r0 += 8) {
+        T part[8][6];
+#pragma unroll
+        for (unsigned u = 0; u < 8; ++u) {
+            const size_t r = r0 + u < geom.ranges ? r0 + u : r0;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) part[u][q] = a.partial[(r * 6 + q) * slots + slot];
+        }
+#pragma unroll
+        for (unsigned u = 0; u < 8; ++u) {
+            if (r0 + u < geom.ranges) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) sum[q] += part[u][q];
+            }
+        }
+    }
+    const T m_first = a.state8[3];
+    const T m_ref   = usable_unit(m_first) ? m_first : T(1);
+    vec4    a1, j1;
+    a1.x = sum[0] * m_ref, a1.y = sum[1] * m_ref, a1.z = sum[2] * m_ref, a1.w = 0;
+    j1.x = sum[3] * m_ref, j1.y = sum[4] * m_ref, j1.z = sum[5] * m_ref, j1.w = 0;
+
+    int                      k     = a.levels[i];
+    k                              = k < 0 ? 0 : (k > a.p.max_level ? a.p.max_level : k);
+    const double             q     = tick_length(a.p);
+    const unsigned long long own   = 1ull << (a.p.max_level - k);
+    const double             dt_i  = static_cast<double>(own) * q;
+    const T                  dt    = static_cast<T>(dt_i);
+    // the corrector of nb_hermite_step_*
+    const T    h = dt * T(0.5), d12 = dt * dt * (T(1) / T(12));
+    const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
+    vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
+    const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
+    const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
+    vec4       x1;
+    const T    v1x = __builtin_fma(d12, j0.x - j1.x, __builtin_fma(h, a0.x + a1.x, v.x));
+    const T    v1y = __builtin_fma(d12, j0.y - j1.y, __builtin_fma(h, a0.y + a1.y, v.y));
+    const T    v1z = __builtin_fma(d12, j0.z - j1.z, __builtin_fma(h, a0.z + a1.z, v.z));
+    x1.x = __builtin_fma(d12, a0.x - a1.x, __builtin_fma(h, v.x + v1x, x.x));
+    x1.y = __builtin_fma(d12, a0.y - a1.y, __builtin_fma(h, v.y + v1y, x.y));
+    x1.z = __builtin_fma(d12, a0.z - a1.z, __builtin_fma(h, v.z + v1z, x.z));
+    x1.w = x.w;
+    v.x = v1x, v.y = v1y, v.z = v1z;
+    reinterpret_cast<vec4*>(a.pos)[i]  = x1;
+    reinterpret_cast<vec4*>(a.vel)[i]  = v;
+    reinterpret_cast<vec4*>(a.acc)[i]  = a1;
+    reinterpret_cast<vec4*>(a.jerk)[i] = j1;
+
+    const double dt_a = aarseth_dt(a0, j0, a1, j1, dt_i, a.p.eta, a.p.dt_max);
+    if (dt_a < dt_i) {
+        while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > dt_a) ++k;
+    } else if (dt_a >= 2.0 * dt_i && k > 0 && now % (2 * own) == 0) {
+        --k;
+    }
+    a.levels[i] = k;
+    a.ticks[i]  = now;
+}
+
+// init: levels from the accelerations and jerks nb_hermite_eval left, ticks 0, the status record cleared
+template <typename T> __global__ __launch_bounds__(256) void block_init_levels(BlockArgs<T> a) {
+    using vec4       = typename Lane<T>::vec4;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0) {
+        BlockStatus s{};
+        *a.status = s;
+        BlockCtrl c{};
+        *a.ctrl = c;
+    }
+    if (i >= a.n) return;
+    const vec4   acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
+    const double want0 = a.p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
+    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : a.p.dt_max;
+    const double q     = tick_length(a.p);
+    int          k     = 0;
+    while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > want) ++k;
+    a.levels[i] = k;
+    a.ticks[i]  = 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void block_sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const unsigned long long* ticks,
+                                                  const BlockStatus* status, unsigned n, BlockParams p) {
+    using vec4       = typename Lane<T>::vec4;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long now = status->now_ticks, tick = ticks[i];
+    const T                  dt  = static_cast<T>(static_cast<double>(now > tick ? now - tick : 0ull) * tick_length(p));
+    const vec4 x = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i];
+    vec4       xp, vp;
+    predict_body<T>(x, v, reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i], dt, xp, vp);
+    vp.w                                 = v.w;
+    reinterpret_cast<vec4*>(pos_out)[i] = xp;
+    reinterpret_cast<vec4*>(vel_out)[i] = vp;
+}
+
+template <typename T, int S> hipError_t launch_eval_s(const BlockArgs<T>& a, unsigned groups, hipStream_t stream) {
+    hipLaunchKernelGGL((hermite_block_eval<T, S>), dim3(groups), dim3(64 * S), 0, stream, static_cast<const T*>(a.state8), static_cast<const unsigned*>(a.active),
+                       static_cast<const BlockCtrl*>(a.ctrl), a.partial, a.n, a.eps2);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+template <typename T> hipError_t launch_block_init(const BlockArgs<T>& a, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block_init_levels<T>), dim3((a.n + 255u) / 256u), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T> hipError_t launch_block_step(const BlockArgs<T>& a, hipStream_t stream) {
+    constexpr unsigned per_tile = 64 * Lane<T>::W;
+    const unsigned     blocks   = (a.n + 255u) / 256u;
+    const unsigned     partials = blocks < kBlockMinPartials ? blocks : kBlockMinPartials;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(block_min_partial, dim3(partials), dim3(256), 0, stream, static_cast<const unsigned long long*>(a.ticks), static_cast<const int*>(a.levels), a.n,
+                       a.p.max_level, a.min_part, a.lvl_part);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL((block_predict_count<T>), dim3(blocks), dim3(256), 0, stream, a, partials);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL(block_scan, dim3(1), dim3(1024), 0, stream, a.counts, blocks, a.ctrl, a.status);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL(block_scatter, dim3(blocks), dim3(256), 0, stream, static_cast<const unsigned long long*>(a.ticks), static_cast<const int*>(a.levels),
+                       static_cast<const unsigned*>(a.counts), static_cast<const BlockCtrl*>(a.ctrl), a.active, a.n, a.p.max_level);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    const unsigned groups = block_launch_groups(a.n, per_tile);
+    hipError_t     err    = hipErrorInvalidValue;
+    switch (block_waves(a.n)) {
+        case 1: err = launch_eval_s<T, 1>(a, groups, stream); break;
+        case 2: err = launch_eval_s<T, 2>(a, groups, stream); break;
+        case 4: err = launch_eval_s<T, 4>(a, groups, stream); break;
+        case 8: err = launch_eval_s<T, 8>(a, groups, stream); break;
+        default: break;
+    }
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((hermite_block_finish<T>), dim3(blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block_sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const unsigned long long* ticks, const BlockStatus* status, unsigned n,
+                             const BlockParams& p, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block_sync<T>), dim3((n + 255u) / 256u), dim3(256), 0, stream, pos_out, vel_out, pos, vel, acc, jerk, ticks, status, n, p);
+    return hipGetLastError();
+}
+
+template hipError_t launch_block_init<float>(const BlockArgs<float>&, hipStream_t);
+template hipError_t launch_block_init<double>(const BlockArgs<double>&, hipStream_t);
+template hipError_t launch_block_step<float>(const BlockArgs<float>&, hipStream_t);
+template hipError_t launch_block_step<double>(const BlockArgs<double>&, hipStream_t);
+template hipError_t launch_block_sync<float>(float*, float*, const float*, const float*, const float*, const float*, const unsigned long long*, const BlockStatus*, unsigned,
+                                             const BlockParams&, hipStream_t);
+template hipError_t launch_block_sync<double>(double*, double*, const double*, const double*, const double*, const double*, const unsigned long long*, const BlockStatus*, unsigned,
+                                              const BlockParams&, hipStream_t);
+
+}  // namespace nb

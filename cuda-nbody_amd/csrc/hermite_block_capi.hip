@@ -1,0 +1,184 @@
+// hermite_block_capi.hip -- the extern "C" boundary of libnbody_hip_hermite_block.so (include/nbody_hip_hermite_block.h).  Every
+// argument is checked on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never
+// synchronises.  The initial evaluation is hermite_eval.o's (linked in; that object exports nothing).
+#include "../../include/nbody_hip_hermite_block.h"
+#include "hermite_block_kernels.h"
+#include "hermite_kernels.h"
+
+#include <cmath>
+#include <cstdint>
+#include <initializer_list>
+
+namespace {
+
+static_assert(NB_HERMITE_BLOCK_MAX_BODIES == nb::kBlockMaxBodies, "the header's limit is the kernels'");
+static_assert(NB_HERMITE_BLOCK_MAX_LEVEL == nb::kBlockMaxLevel, "the header's deepest level is the kernels'");
+static_assert(NB_HERMITE_BLOCK_STOPPED == nb::kBlockStopped, "the header's flag is the kernels'");
+static_assert(sizeof(nb_hermite_block_status_t) == 64 && sizeof(nb::BlockStatus) == 64, "the status record is 64 bytes");
+static_assert(sizeof(nb_hermite_block_params_t) == sizeof(nb::BlockParams), "the parameters cross by value");
+static_assert(sizeof(nb::BlockCtrl) == 64, "the control record is 64 bytes");
+
+struct Span {
+    const void*    p;
+    std::uintptr_t bytes;
+    std::uintptr_t align;
+};
+
+bool size_ok(unsigned n) { return n >= 1 && n <= nb::kBlockMaxBodies; }
+
+// no null, every span aligned, no two spans overlapping
+bool spans_ok(std::initializer_list<Span> spans) {
+    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
+    for (const Span& s : spans) {
+        if (s.p == nullptr || addr(s.p) % s.align != 0) return false;
+    }
+    for (const Span* x = spans.begin(); x != spans.end(); ++x) {
+        for (const Span* y = x + 1; y != spans.end(); ++y) {
+            if (addr(x->p) < addr(y->p) + y->bytes && addr(y->p) < addr(x->p) + x->bytes) return false;
+        }
+    }
+    return true;
+}
+
+bool params_ok(const nb_hermite_block_params_t* p) {
+    if (p == nullptr) return false;
+    const auto positive = [](double v) { return std::isfinite(v) && v > 0; };
+    return positive(p->eta) && positive(p->eta_start) && positive(p->dt_max) && p->max_level >= 0 && p->max_level <= nb::kBlockMaxLevel &&
+           std::isnormal(std::ldexp(p->dt_max, -p->max_level));
+}
+
+nb::BlockParams params_of(const nb_hermite_block_params_t* p) { return nb::BlockParams{p->eta, p->eta_start, p->dt_max, p->max_level, 0}; }
+
+template <typename T> T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
+
+template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_block_plan_t* out) {
+    if (out == nullptr || !size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
+    constexpr unsigned  per_tile = sizeof(T) == 4 ? 128 : 64;
+    const nb::BlockGeom g        = nb::block_geometry(n, n_active, per_tile);
+    const unsigned      S        = nb::block_waves(n);
+    out->bodies_per_lane         = per_tile / 64;
+    out->waves_per_group         = static_cast<int>(S);
+    out->unroll                  = sizeof(T) == 4 ? 4 : 2;
+    out->tiles                   = g.tiles;
+    out->ranges                  = g.ranges;
+    out->groups                  = g.tiles * g.ranges;
+    out->launch_groups           = nb::block_launch_groups(n, per_tile);
+    out->block_threads           = 64 * S;
+    out->lds_bytes               = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * per_tile * sizeof(T)) + 128;
+    out->slots                   = g.tiles * per_tile;
+    out->chunks                  = nb::block_chunks(n);
+    out->launches                = 6;
+    out->partial_offset          = nb::block_layout(n, sizeof(T)).partial;
+    out->partial_bytes           = static_cast<unsigned long long>(g.ranges) * 6 * out->slots * sizeof(T);
+    return 0;
+}
+
+// the arrays of a system and the workspace, checked; fills `a`
+template <typename T>
+bool bind(nb::BlockArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace, size_t workspace_bytes,
+          unsigned n, const nb_hermite_block_params_t* params) {
+    if (!size_ok(n) || !params_ok(params)) return false;
+    const nb::BlockLayout l = nb::block_layout(n, sizeof(T));
+    if (workspace_bytes < l.bytes) return false;
+    const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
+    if (!spans_ok({{pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {ticks, static_cast<std::uintptr_t>(n) * 8, 8},
+                   {levels, static_cast<std::uintptr_t>(n) * 4, 4}, {status, 64, 8}, {workspace, l.bytes, 32}})) {
+        return false;
+    }
+    char* const ws = static_cast<char*>(workspace);
+    a.pos = pos, a.vel = vel, a.acc = acc, a.jerk = jerk;
+    a.ticks    = reinterpret_cast<unsigned long long*>(ticks);
+    a.levels   = levels;
+    a.status   = reinterpret_cast<nb::BlockStatus*>(status);
+    a.state8   = reinterpret_cast<T*>(ws + l.state8);
+    a.partial  = reinterpret_cast<T*>(ws + l.partial);
+    a.active   = reinterpret_cast<unsigned*>(ws + l.active);
+    a.counts   = reinterpret_cast<unsigned*>(ws + l.counts);
+    a.min_part = reinterpret_cast<unsigned long long*>(ws + l.min_part);
+    a.lvl_part = reinterpret_cast<int*>(ws + l.lvl_part);
+    a.ctrl     = reinterpret_cast<nb::BlockCtrl*>(ws + l.ctrl);
+    a.n        = n;
+    a.p        = params_of(params);
+    a.t_stop   = 0;
+    return true;
+}
+
+template <typename T>
+int init(T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace, size_t workspace_bytes, unsigned n, T eps2,
+         const nb_hermite_block_params_t* params, nb_stream_t stream) {
+    nb::BlockArgs<T> a{};
+    if (!bind(a, pos, vel, acc, jerk, ticks, levels, status, workspace, workspace_bytes, n, params)) return NB_ERR_INVALID_ARGUMENT;
+    a.eps2 = floored(eps2);
+    nb::HermiteArgs<T> e{};
+    e.pos = pos, e.vel_in = vel, e.acc = acc, e.jerk = jerk, e.n = n, e.eps2 = a.eps2;
+    if (const auto err = nb::launch_hermite_eval<T>(e, static_cast<hipStream_t>(stream)); err != hipSuccess) return static_cast<int>(err);
+    return static_cast<int>(nb::launch_block_init<T>(a, static_cast<hipStream_t>(stream)));
+}
+
+template <typename T>
+int step(T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace, size_t workspace_bytes, unsigned n, T eps2,
+         const nb_hermite_block_params_t* params, double t_stop, nb_stream_t stream) {
+    nb::BlockArgs<T> a{};
+    if (std::isnan(t_stop)) return NB_ERR_INVALID_ARGUMENT;
+    if (!bind(a, pos, vel, acc, jerk, ticks, levels, status, workspace, workspace_bytes, n, params)) return NB_ERR_INVALID_ARGUMENT;
+    a.eps2   = floored(eps2);
+    a.t_stop = t_stop;
+    return static_cast<int>(nb::launch_block_step<T>(a, static_cast<hipStream_t>(stream)));
+}
+
+template <typename T>
+int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const uint64_t* ticks, const nb_hermite_block_status_t* status, unsigned n,
+         const nb_hermite_block_params_t* params, nb_stream_t stream) {
+    if (!size_ok(n) || !params_ok(params)) return NB_ERR_INVALID_ARGUMENT;
+    const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
+    if (!spans_ok({{pos_out, bodies, al}, {vel_out, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al},
+                   {ticks, static_cast<std::uintptr_t>(n) * 8, 8}, {status, 64, 8}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
+    return static_cast<int>(nb::launch_block_sync<T>(pos_out, vel_out, pos, vel, acc, jerk, reinterpret_cast<const unsigned long long*>(ticks),
+                                                     reinterpret_cast<const nb::BlockStatus*>(status), n, params_of(params), static_cast<hipStream_t>(stream)));
+}
+
+}  // namespace
+
+extern "C" {
+
+int nb_hermite_block_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
+    if (bytes == nullptr || !size_ok(num_bodies) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    *bytes = nb::block_layout(num_bodies, sizeof_T).bytes;
+    return 0;
+}
+
+int nb_hermite_block_plan_f32(unsigned num_bodies, unsigned num_active, nb_hermite_block_plan_t* plan) { return plan_query<float>(num_bodies, num_active, plan); }
+int nb_hermite_block_plan_f64(unsigned num_bodies, unsigned num_active, nb_hermite_block_plan_t* plan) { return plan_query<double>(num_bodies, num_active, plan); }
+
+int nb_hermite_block_init_f32(float* positions, float* velocities, float* accelerations, float* jerks, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status,
+                              void* workspace, size_t workspace_bytes, unsigned num_bodies, float softening_sq, const nb_hermite_block_params_t* params, nb_stream_t stream) {
+    return init<float>(positions, velocities, accelerations, jerks, ticks, levels, status, workspace, workspace_bytes, num_bodies, softening_sq, params, stream);
+}
+int nb_hermite_block_init_f64(double* positions, double* velocities, double* accelerations, double* jerks, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status,
+                              void* workspace, size_t workspace_bytes, unsigned num_bodies, double softening_sq, const nb_hermite_block_params_t* params, nb_stream_t stream) {
+    return init<double>(positions, velocities, accelerations, jerks, ticks, levels, status, workspace, workspace_bytes, num_bodies, softening_sq, params, stream);
+}
+
+int nb_hermite_block_step_f32(float* positions, float* velocities, float* accelerations, float* jerks, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status,
+                              void* workspace, size_t workspace_bytes, unsigned num_bodies, float softening_sq, const nb_hermite_block_params_t* params, double t_stop,
+                              nb_stream_t stream) {
+    return step<float>(positions, velocities, accelerations, jerks, ticks, levels, status, workspace, workspace_bytes, num_bodies, softening_sq, params, t_stop, stream);
+}
+int nb_hermite_block_step_f64(double* positions, double* velocities, double* accelerations, double* jerks, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status,
+                              void* workspace, size_t workspace_bytes, unsigned num_bodies, double softening_sq, const nb_hermite_block_params_t* params, double t_stop,
+                              nb_stream_t stream) {
+    return step<double>(positions, velocities, accelerations, jerks, ticks, levels, status, workspace, workspace_bytes, num_bodies, softening_sq, params, t_stop, stream);
+}
+
+int nb_hermite_block_sync_f32(float* positions_out, float* velocities_out, const float* positions, const float* velocities, const float* accelerations, const float* jerks,
+                              const uint64_t* ticks, const nb_hermite_block_status_t* status, unsigned num_bodies, const nb_hermite_block_params_t* params, nb_stream_t stream) {
+    return sync<float>(positions_out, velocities_out, positions, velocities, accelerations, jerks, ticks, status, num_bodies, params, stream);
+}
+int nb_hermite_block_sync_f64(double* positions_out, double* velocities_out, const double* positions, const double* velocities, const double* accelerations, const double* jerks,
+                              const uint64_t* ticks, const nb_hermite_block_status_t* status, unsigned num_bodies, const nb_hermite_block_params_t* params, nb_stream_t stream) {
+    return sync<double>(positions_out, velocities_out, positions, velocities, accelerations, jerks, ticks, status, num_bodies, params, stream);
+}
+
+}  // extern "C"

@@ -24,37 +24,7 @@ namespace {
 
 #include "nbody_lane.h"
 
-constexpr int kChunk      = 128;  // bodies j per wave and chunk
-constexpr int kFlushEvery = 8;    // chunks a register sum may collect
-template <typename T> constexpr int unroll_for() { return sizeof(T) == 8 ? 2 : 4; }  // U: a body j is 8 (fp32) / 16 (fp64) scalar registers
-
-// s^-2 and s^-3 from s2.  fp32: v_rsq_f32 (1 ulp) and two products.  fp64: the v_rsq_f64 seed y0 (relative error <= 2^-23) and, with
-// r = 1 - s2 y0^2 (|r| <= 2^-22), the series of Lane<double>::coupling for y0^3 (1-r)^(-3/2) and y0^2 (1 + r + r^2) for y0^2 / (1-r).
-template <typename T> struct Powers;
-template <> struct Powers<float> {
-    using vec = Lane<float>::vec;
-    static __device__ __forceinline__ void of(vec s2, const Lane<float>::Consts&, vec& inv2, vec& inv3) {
-        const vec inv = vec{__builtin_amdgcn_rsqf(s2.x), __builtin_amdgcn_rsqf(s2.y)};
-        inv2          = inv * inv;
-        inv3          = inv * inv2;
-    }
-};
-template <> struct Powers<double> {
-    static __device__ __forceinline__ void of(double s2, const Lane<double>::Consts& k, double& inv2, double& inv3) {
-        const double y0 = __builtin_amdgcn_rsq(s2);
-        const double t0 = y0 * y0;
-        const double r  = __builtin_fma(-s2, t0, 1.0);
-        const double c  = y0 * t0;
-        const double w  = r * __builtin_fma(r, k.c1875, k.c15);
-        inv3            = __builtin_fma(c, w, c);
-        const double q  = __builtin_fma(r, r, r);
-        inv2            = __builtin_fma(t0, q, t0);
-    }
-};
-
-template <typename T> struct BodyJ {
-    typename Lane<T>::raw4 p, v;  // {x, y, z, m}, {vx, vy, vz, -} in scalar registers
-};
+#include "hermite_stream.h"
 
 template <typename T, int S, bool STEP>
 __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_eval(HermiteArgs<T> a) {
@@ -131,65 +101,7 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         }
     };
 
-    // UB bodies j against the lane's vector of bodies i, written stage by stage: UB independent chains in flight
-    auto compute = [&]<bool UNIT, int UB>(const BodyJ<T>* b, vec (&sum)[6]) {
-        vec dx[UB], dy[UB], dz[UB], ex[UB], ey[UB], ez[UB], s2[UB], rv[UB], k3[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            dx[u] = LT::splat(b[u].p.x) - px, dy[u] = LT::splat(b[u].p.y) - py, dz[u] = LT::splat(b[u].p.z) - pz;
-            ex[u] = LT::splat(b[u].v.x) - vx, ey[u] = LT::splat(b[u].v.y) - vy, ez[u] = LT::splat(b[u].v.z) - vz;
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) s2[u] = LT::fma(dx[u], dx[u], eps2), rv[u] = dx[u] * ex[u];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) s2[u] = LT::fma(dy[u], dy[u], s2[u]), rv[u] = LT::fma(dy[u], ey[u], rv[u]);
-#pragma unroll
-        for (int u = 0; u < UB; ++u) s2[u] = LT::fma(dz[u], dz[u], s2[u]), rv[u] = LT::fma(dz[u], ez[u], rv[u]);
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            vec inv2;
-            Powers<T>::of(s2[u], consts, inv2, k3[u]);
-            rv[u] = (rv[u] * inv2) * minus3;  // -3 (r.w) / s^2
-            if constexpr (!UNIT) k3[u] = k3[u] * LT::splat(b[u].p.w);
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) ex[u] = LT::fma(rv[u], dx[u], ex[u]), ey[u] = LT::fma(rv[u], dy[u], ey[u]), ez[u] = LT::fma(rv[u], dz[u], ez[u]);
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            sum[0] = LT::fma(dx[u], k3[u], sum[0]), sum[1] = LT::fma(dy[u], k3[u], sum[1]), sum[2] = LT::fma(dz[u], k3[u], sum[2]);
-            sum[3] = LT::fma(ex[u], k3[u], sum[3]), sum[4] = LT::fma(ey[u], k3[u], sum[4]), sum[5] = LT::fma(ez[u], k3[u], sum[5]);
-        }
-    };
-    // a group of U bodies j in stage blocks of UB: fp32 2 x 2 (four chains' temporaries at once took the kernel to 127 VGPRs, and the
-    // S = 1 instantiation into scratch; two blocks of two compile to 93 - 95), fp64 one block of 2
-    constexpr int UB = sizeof(T) == 8 ? U : U / 2;
-    auto whole = [&]<bool UNIT>(const BodyJ<T> (&b)[U]) {
-#pragma unroll
-        for (int h = 0; h < U; h += UB) compute.template operator()<UNIT, UB>(b + h, first);
-    };
-    auto arrived = [](const BodyJ<T> (&b)[U]) { asm volatile("" : : "s"(b[0].p) : "memory"); };  // what follows is issued after the set's wait
-    // b0 holds (or is loading) group 0 of the chunk at body `chunk`; on return it is loading the first group at body `next`
-    auto stream = [&]<bool UNIT>(size_t chunk, unsigned groups, size_t next, BodyJ<T> (&b0)[U], BodyJ<T> (&b1)[U]) {
-        unsigned g = 0;
-#pragma unroll 1
-        for (; g + 2 <= groups; g += 2) {
-            arrived(b0);
-            group(chunk + (g + 1) * U, b1);
-            __builtin_amdgcn_sched_barrier(0);  // (the load stays ahead of the compute it overlaps)
-            whole.template operator()<UNIT>(b0);
-            arrived(b1);
-            group(g + 2 < groups ? chunk + (g + 2) * U : next, b0);
-            __builtin_amdgcn_sched_barrier(0);
-            whole.template operator()<UNIT>(b1);
-        }
-        if (g < groups) whole.template operator()<UNIT>(b0);  // (odd count: the ragged last chunk, nothing follows it)
-    };
-    T    pending_scale = T(1);  // what `first` is still to be multiplied by
-    auto flush         = [&]() {
-        const vec scale = LT::splat(pending_scale);
-#pragma unroll
-        for (int q = 0; q < 6; ++q) second[q] = LT::fma(first[q], scale, second[q]), first[q] = LT::splat(0);
-    };
+#include "hermite_stream.inc"
 
     // The SIMD arbiter is oldest-first: left alone, the waves that share a SIMD finish equal shares of work one after the other and
     // the last runs alone at a lower issue rate (nbody_fast_stream.inc has the measurements).  As there, each wave publishes how many

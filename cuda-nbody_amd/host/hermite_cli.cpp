@@ -2,6 +2,7 @@
 #include "hermite_cli.hpp"
 
 #include "bodysystemhip_hermite.hpp"
+#include "bodysystemhip_hermite_block.hpp"
 #include "compute.hpp"
 #include "randomise_bodies.hpp"
 #include "text.hpp"
@@ -16,7 +17,7 @@
 namespace {
 
 // nb_energy_* of the product library on the system's arrays (softening^2 is that library's process-global setting)
-template <typename T> auto energy_of(const BodySystemHIPHermite<T>& system, T softening_sq) -> nb_energy_t {
+template <typename System, typename T> auto energy_of(const System& system, T softening_sq) -> nb_energy_t {
     const auto  n     = static_cast<unsigned>(system.num_bodies());
     std::size_t bytes = 0;
     hip_check(nb_energy_workspace_bytes(n, &bytes), "nb_energy_workspace_bytes");
@@ -38,9 +39,9 @@ auto print_energy(const std::string& what, const nb_energy_t& e) -> void {
     std::printf("%s: kinetic=%.9g potential=%.9g total=%.9g momentum=%.9g,%.9g,%.9g", what.c_str(), e.kinetic, e.potential, e.total, e.momentum[0], e.momentum[1], e.momentum[2]);
 }
 
-template <typename T> auto run_typed(const HermiteRun& run) -> void {
-    const auto     n = run.num_bodies;
-    std::vector<T> pos(4 * n), vel(4 * n);
+// the single-system start-up state (Compute's constructor)
+template <typename T> auto startup_state(const HermiteRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+    const auto n = run.num_bodies;
     {
         // the single-system start-up state (Compute's constructor): an fp32 and an fp64 system reset with demo row 0's scales, then
         // the active precision with the N-scaled ones
@@ -53,6 +54,79 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         Compute::scale_params_for(n, scaled);
         randomise_bodies<T>(run.config, pos, vel, scaled.cluster_scale, scaled.velocity_scale);
     }
+}
+
+template <typename T> auto write_dump(const HermiteRun& run, const std::vector<T>& pos, const std::vector<T>& vel) -> void {
+    auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
+    if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
+    out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
+    out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
+}
+
+// --integrator=hermite-block: dt_max = dt, --steps=K advances to K dt, --benchmark times `iterations` intervals of dt after one untimed;
+// interactions are counted as the status record counts them: sum of n_act * N
+template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
+    const auto     n = run.num_bodies;
+    std::vector<T> pos(4 * n), vel(4 * n);
+    startup_state<T>(run, pos, vel);
+    const double dt_max = static_cast<double>(static_cast<T>(run.params.time_step));
+    const T      softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
+    const auto   params = nb_hermite_block_params_t{run.eta, 0.01, dt_max, run.levels, 0};
+    auto         system = BodySystemHIPHermiteBlock<T>(n, softening_sq, params);
+    system.set_state(pos, vel);
+    const auto measure = run.energy && (run.benchmark || run.steps > 0);
+    nb_energy_t start{};
+    if (measure) {
+        system.sync();
+        start = energy_of(system, softening_sq);
+    }
+    const auto report = [&](const char* what, const nb_hermite_block_status_t& from, const nb_hermite_block_status_t& to) {
+        const auto   body_steps = to.body_steps - from.body_steps;
+        const double evaluations = static_cast<double>(body_steps) / static_cast<double>(n);
+        std::printf("%s%llu block steps, %llu body steps = %s evaluations of N^2 interactions, deepest level %d\n", what, static_cast<unsigned long long>(to.block_steps - from.block_steps),
+                    static_cast<unsigned long long>(body_steps), text::width3(static_cast<float>(evaluations)).c_str(), to.deepest_level);
+    };
+    const auto report_energy = [&](std::size_t intervals) {
+        if (!measure) return;
+        system.sync();
+        const auto end = energy_of(system, softening_sq);
+        print_energy("energy start", start);
+        std::printf("\n");
+        print_energy("energy end (" + std::to_string(intervals) + " steps)", end);
+        std::printf(" relative_drift=%.9g\n", (end.total - start.total) / std::abs(start.total));
+    };
+    if (run.benchmark) {
+        const auto warm = system.advance(dt_max);  // (untimed, as Compute::run_benchmark)
+        HipEvent   begin, stop;
+        begin.record();
+        const auto end = system.advance(static_cast<double>(1 + run.iterations) * dt_max);
+        stop.record();
+        stop.synchronize();
+        const float  milliseconds = HipEvent::elapsed_ms(begin, stop);
+        const double interactions = static_cast<double>(end.body_steps - warm.body_steps) * static_cast<double>(n);
+        std::printf("%zu bodies, hermite-block integrator, total time for %d intervals of dt_max: %s ms\n", n, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("= %s ms per interval\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
+        report("= ", warm, end);
+        std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
+        report_energy(1 + static_cast<std::size_t>(run.iterations));
+        return;
+    }
+    const auto none = system.status();
+    const auto end  = run.steps > 0 ? system.advance(static_cast<double>(run.steps) * dt_max) : none;
+    if (!run.dump.empty()) {
+        system.sync();
+        system.get_positions(pos);
+        system.get_velocities(vel);
+        write_dump<T>(run, pos, vel);
+    }
+    report("", none, end);
+    report_energy(run.steps);
+}
+
+template <typename T> auto run_typed(const HermiteRun& run) -> void {
+    const auto     n = run.num_bodies;
+    std::vector<T> pos(4 * n), vel(4 * n);
+    startup_state<T>(run, pos, vel);
     // BodySystemHIP's conversions: dt float -> T, softening^2 = T(s) * T(s)
     const T dt = static_cast<T>(run.params.time_step);
     const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
@@ -94,10 +168,7 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
     if (!run.dump.empty()) {
         system.get_positions(pos);
         system.get_velocities(vel);
-        auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
-        if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
-        out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
-        out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
+        write_dump<T>(run, pos, vel);
     }
     report_energy(run.steps);
 }
@@ -105,5 +176,9 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
 }  // namespace
 
 auto run_hermite(const HermiteRun& run) -> void {
+    if (run.block) {
+        if (run.fp64) run_block_typed<double>(run); else run_block_typed<float>(run);
+        return;
+    }
     if (run.fp64) run_typed<double>(run); else run_typed<float>(run);
 }

@@ -1,4 +1,5 @@
-// hermite_cli.hpp -- `nbody --integrator=hermite`: the single-system run stepped by the 4th-order Hermite scheme (BodySystemHIPHermite).
+// hermite_cli.hpp -- `nbody --integrator=hermite`: the single-system run stepped by the 4th-order Hermite scheme (BodySystemHIPHermite),
+// and `nbody --integrator=hermite-block`: the same run with block time steps (BodySystemHIPHermiteBlock).
 #pragma once
 
 #include "nbody_types.hpp"
@@ -16,6 +17,9 @@ struct HermiteRun {
     std::size_t           steps = 0;
     std::filesystem::path dump;
     bool                  energy = false;
+    bool                  block = false;  // --integrator=hermite-block: dt_max = the demo row's dt, `steps` / `iterations` count intervals of dt_max
+    double                eta = 0.02;     // --eta (the first steps use eta_start = 0.01)
+    int                   levels = 30;    // --levels: steps down to dt_max * 2^-levels
 };
 
 // Starts from the current rand() state (main has applied --seed) with the single-system start-up state (the same three

@@ -9,9 +9,11 @@
 //                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
+//                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
 #include "ensemble_cli.hpp"
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
+#include "../../include/nbody_hip_hermite_block.h"
 #include "compute.hpp"
 #include "integrate_nbody_hip.hpp"
 
@@ -64,7 +66,10 @@ struct Options {
     std::optional<std::size_t> demo;   // row of Compute::demo_params (the reference reaches them from the viewer's keys only)
     double                inject_error = 0.0;
     std::size_t           systems = 0;  // --systems=<B>: an ensemble of B systems (0: one system, the reference's run)
-    bool                  hermite = false;  // --integrator=hermite (euler, the reference's step, is the default)
+    bool                  hermite = false;  // --integrator=hermite or hermite-block (euler, the reference's step, is the default)
+    bool                  hermite_block = false;  // --integrator=hermite-block
+    std::optional<double> eta;     // --eta (hermite-block)
+    std::optional<int>    levels;  // --levels (hermite-block)
 };
 
 constexpr auto help_text = R"(The MI355X NBody hot path (drop-in for cuda-nbody's compute path).
@@ -103,9 +108,12 @@ Options:
   --systems UINT              Step this many independent systems of --numbodies (<= 65536, required) bodies in one launch: system 0
                               is the single-system start-up state, the others the next draws; --benchmark counts B*N^2 interactions
                               per step, --dump writes every system's positions, then every system's velocities
-  --integrator TEXT [euler]   euler | hermite.  hermite: 4th-order Hermite predictor-corrector steps (acceleration and jerk per
-                              interaction, no damping) of --numbodies (required) bodies on one device, FAST arithmetic; with
-                              --benchmark, --steps, --dump and --energy
+  --integrator TEXT [euler]   euler | hermite | hermite-block.  hermite: 4th-order Hermite predictor-corrector steps (acceleration and
+                              jerk per interaction, no damping) of --numbodies (required) bodies on one device, FAST arithmetic; with
+                              --benchmark, --steps, --dump and --energy.  hermite-block: the same scheme with block time steps: every
+                              body steps by its own dt * 2^-level, --steps=K advances to K * dt, interactions are counted as n_act * N
+  --eta FLOAT [0.02]          hermite-block: accuracy parameter of the bodies' time steps (the first steps use 0.01)
+  --levels UINT [30]          hermite-block: the deepest level, 0 to 40 (time steps down to dt * 2^-levels)
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
 
@@ -245,8 +253,25 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
         } else if (name == "integrator") {
             const auto v = take_value();
-            ok           = v && (*v == "euler" || *v == "hermite");
-            if (ok) options.hermite = *v == "hermite";
+            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite-block");
+            if (ok) options.hermite = *v != "euler", options.hermite_block = *v == "hermite-block";
+        } else if (name == "eta") {
+            const auto v = take_value();
+            ok           = v.has_value();
+            if (ok) {
+                char*      end  = nullptr;
+                const auto text = std::string(*v);
+                const auto eta  = std::strtod(text.c_str(), &end);
+                ok              = end != nullptr && *end == '\0' && end != text.c_str() && eta > 0.0 && eta <= 1.0;
+                if (!ok) return error("--eta: Value not in range (0, 1]");
+                options.eta = eta;
+            }
+        } else if (name == "levels") {
+            const auto v = take_value();
+            int        l = 0;
+            ok           = v && parse_number(*v, l) && l >= 0 && l <= NB_HERMITE_BLOCK_MAX_LEVEL;
+            if (!ok) return error("--levels: Value not in range 0 to 40");
+            options.levels = l;
         } else if (name == "config") {
             const auto v = take_value();
             ok           = v && (*v == "shell" || *v == "random" || *v == "expand");
@@ -274,6 +299,7 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
     if (options.hermite) {
         if (options.numbodies == 0) return error("--integrator=hermite needs an explicit --numbodies");
         if (options.numbodies > NB_HERMITE_MAX_BODIES) return error("--integrator=hermite: --numbodies must be at most 67108864");
+        if (options.hermite_block && options.numbodies > NB_HERMITE_BLOCK_MAX_BODIES) return error("--integrator=hermite-block: --numbodies must be at most 16777216");
         if (options.mode == NB_MODE_STRICT) return error("--integrator=hermite has no strict mode: there is no CPU reference arithmetic to reproduce");
         if (options.devices.size() > 1) return error("--integrator=hermite is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
         if (options.systems > 0) return error("--integrator=hermite cannot be combined with --systems");
@@ -281,6 +307,8 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             return error("--integrator=hermite cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --no-workspace, --workspace-mib or --cpu");
         }
     }
+
+    if ((options.eta || options.levels) && !options.hermite_block) return error("--eta and --levels belong to --integrator=hermite-block");
 
     // the reference prints this hint and the full help on every successful parse (nbody.cpp:315-316)
     std::printf("Run \" nbody - benchmark[-numbodies = <numBodies>] \" to measure performance\n");
@@ -351,6 +379,9 @@ auto main(int argc, char** argv) -> int {
             run.steps      = cmd_options.steps;
             run.dump       = cmd_options.dump;
             run.energy     = cmd_options.energy;
+            run.block      = cmd_options.hermite_block;
+            run.eta        = cmd_options.eta.value_or(run.eta);
+            run.levels     = cmd_options.levels.value_or(run.levels);
             run_hermite(run);
             return 0;
         }
