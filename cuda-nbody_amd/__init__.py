@@ -32,6 +32,8 @@ ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_ENSEMBLE_LIB", os.path.join(HERE, 
 HERMITE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_LIB", os.path.join(HERE, "libnbody_hip_hermite.so"))
 # Hermite steps with block time steps (include/nbody_hip_hermite_block.h) are a fifth, loaded by hermite_block_lib().
 HERMITE_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_LIB", os.path.join(HERE, "libnbody_hip_hermite_block.so"))
+# Nearest neighbours, potentials and neighbour lists (include/nbody_hip_neighbour.h) are a sixth, loaded by neighbour_lib().
+NEIGHBOUR_LIB_PATH = os.environ.get("NBODY_HIP_NEIGHBOUR_LIB", os.path.join(HERE, "libnbody_hip_neighbour.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -291,7 +293,39 @@ HERMITE_BLOCK_SIGNATURES = {
     "nb_hermite_block_sync_f64": (_ci, [_vp] * 8 + [_cu, _P(HermiteBlockParams), _vp]),
 }
 
+
+# include/nbody_hip_neighbour.h: exported by libnbody_hip_neighbour.so, and nothing else is
+class NeighbourStatus(ctypes.Structure):
+    """nb_neighbour_status_t: 64 bytes of device memory every survey and lists call writes"""
+    _fields_ = [("total_neighbours", ctypes.c_uint64), ("closest_dist_sq", _cd), ("closest_i", ctypes.c_uint32), ("closest_j", ctypes.c_uint32),
+                ("max_count", ctypes.c_uint32), ("max_count_body", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+class NeighbourPlan(ctypes.Structure):
+    """nb_neighbour_plan_t: the geometry of the survey and the lists, a function of N and the precision"""
+    _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("unroll", _ci), ("tiles", _cu), ("block_threads", _cu), ("lds_bytes", _cu),
+                ("chunks", _cu), ("list_ranges", _cu), ("list_groups", _cu), ("survey_launches", _cu), ("list_launches", _cu), ("reserved", _cu),
+                ("planes_offset", ctypes.c_ulonglong), ("planes_bytes", ctypes.c_ulonglong)]
+
+
+NEIGHBOUR_MAX_BODIES = 1 << 24
+NEIGHBOUR_NONE = 0xFFFFFFFF
+NEIGHBOUR_OVERFLOW = 1
+_ull = ctypes.c_ulonglong
+NEIGHBOUR_SIGNATURES = {
+    "nb_neighbour_workspace_bytes": (_ci, [_cu, _cu, _P(_sz)]),
+    "nb_neighbour_plan_f32": (_ci, [_cu, _P(NeighbourPlan)]),
+    "nb_neighbour_plan_f64": (_ci, [_cu, _P(NeighbourPlan)]),
+    # positions N radius_sq radii_sq softening_sq | nearest_index nearest_dist_sq counts potentials | status workspace workspace_bytes stream
+    "nb_neighbour_survey_f32": (_ci, [_vp, _cu, _cf, _vp, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nb_neighbour_survey_f64": (_ci, [_vp, _cu, _cd, _vp, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # positions N radius_sq radii_sq | offsets indices capacity | status workspace workspace_bytes stream
+    "nb_neighbour_lists_f32": (_ci, [_vp, _cu, _cf, _vp, _vp, _vp, _ull, _vp, _vp, _sz, _vp]),
+    "nb_neighbour_lists_f64": (_ci, [_vp, _cu, _cd, _vp, _vp, _vp, _ull, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
+_neighbour_lib = None
 _ensemble_lib = None
 _hermite_lib = None
 _hermite_block_lib = None
@@ -370,6 +404,21 @@ def hermite_block_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _hermite_block_lib = handle
     return _hermite_block_lib
+
+
+def neighbour_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_neighbour.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _neighbour_lib
+    if _neighbour_lib is None:
+        if not os.path.exists(NEIGHBOUR_LIB_PATH):
+            raise FileNotFoundError(f"{NEIGHBOUR_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(NEIGHBOUR_LIB_PATH)
+        for name, (restype, argtypes) in NEIGHBOUR_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _neighbour_lib = handle
+    return _neighbour_lib
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -879,6 +928,144 @@ class HermiteBlockSystem:
 
     def synchronize(self) -> None:
         check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+def neighbour_plan(num_bodies: int, dtype=np.float32) -> NeighbourPlan:
+    """nb_neighbour_plan_*: the geometry of a survey and of the lists of `num_bodies` bodies"""
+    p = NeighbourPlan()
+    fn = neighbour_lib().nb_neighbour_plan_f32 if np.dtype(dtype) == np.float32 else neighbour_lib().nb_neighbour_plan_f64
+    check(fn(num_bodies, ctypes.byref(p)), "nb_neighbour_plan")
+    return p
+
+
+def neighbour_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(neighbour_lib().nb_neighbour_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_neighbour_workspace_bytes")
+    return out.value
+
+
+def neighbour_status_dict(status: NeighbourStatus) -> dict:
+    return {name: getattr(status, name) for name, _ in NeighbourStatus._fields_ if name != "reserved"}
+
+
+class NeighbourSurvey:
+    """Nearest neighbours, counts, potentials and neighbour lists of states of N bodies (include/nbody_hip_neighbour.h).
+
+    The outputs, the status record, the workspace and a staging copy of the positions are device buffers owned here.  ``positions`` is
+    a device address (a DeviceBuffer, its ``ptr`` or an int: T[4 N], only read) or a host array of shape (N, 4) {x, y, z, m};
+    ``radii_sq`` likewise (T[N]).  ``survey`` and ``lists`` enqueue on `stream`, wait for it and return numpy arrays plus the status
+    record as a dict; ``enqueue_survey`` / ``enqueue_lists`` only enqueue (outputs stay on the device: see the ``*_ptr`` attributes)."""
+
+    def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=0.0):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies = n = int(num_bodies)
+        self.softening_sq = self.dtype.type(softening_sq)
+        self._workspace_bytes = neighbour_workspace_bytes(n, self.dtype)  # refuses the sizes the calls refuse
+        size = self.dtype.itemsize
+        self._pos, self._radii = DeviceBuffer(4 * n * size), DeviceBuffer(n * size)
+        self._nearest, self._counts = DeviceBuffer(4 * n), DeviceBuffer(4 * n)
+        self._nearest_d2, self._potentials = DeviceBuffer(n * size), DeviceBuffer(n * size)
+        self._offsets = DeviceBuffer(8 * (n + 1))
+        self._indices = None
+        self._status = DeviceBuffer(ctypes.sizeof(NeighbourStatus))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+
+    def _buffers(self):
+        return [b for b in (self._pos, self._radii, self._nearest, self._counts, self._nearest_d2, self._potentials, self._offsets, self._indices, self._status,
+                            self._workspace) if b is not None]
+
+    def _device(self, data, own: DeviceBuffer, shape):
+        """the device address of `data`: its own when it is one, else a host array uploaded into `own`"""
+        if isinstance(data, DeviceBuffer):
+            return data.ptr
+        if isinstance(data, (int, ctypes.c_void_p)):
+            return data
+        host = np.ascontiguousarray(data, dtype=self.dtype)
+        if host.shape != shape:
+            raise ValueError(f"expected an array of shape {shape}, got {host.shape}")
+        own.upload(host)
+        return own.ptr
+
+    def _radius(self, radius_sq, radii_sq):
+        if (radius_sq is None) == (radii_sq is None):
+            raise ValueError("give radius_sq or radii_sq")
+        if radii_sq is None:
+            return self._scalar(radius_sq), None
+        return self._scalar(0), self._device(radii_sq, self._radii, (self.num_bodies,))
+
+    def enqueue_survey(self, positions, radius_sq=None, radii_sq=None, potentials=False, stream=None) -> None:
+        radius, radii = self._radius(radius_sq, radii_sq)
+        fn = getattr(neighbour_lib(), "nb_neighbour_survey_" + self._suffix)
+        check(fn(self._device(positions, self._pos, (self.num_bodies, 4)), self.num_bodies, radius, radii, self._scalar(self.softening_sq), self._nearest.ptr,
+                 self._nearest_d2.ptr, self._counts.ptr, self._potentials.ptr if potentials else None, self._status.ptr, self._workspace.ptr,
+                 self._workspace_bytes, stream), "nb_neighbour_survey")
+
+    def enqueue_lists(self, positions, radius_sq=None, radii_sq=None, capacity: int = 0, stream=None) -> None:
+        radius, radii = self._radius(radius_sq, radii_sq)
+        capacity = int(capacity)
+        if capacity > 0 and (self._indices is None or self._indices.nbytes < 4 * capacity):
+            if self._indices is not None:
+                self._indices.free()
+            self._indices = DeviceBuffer(4 * capacity)
+        fn = getattr(neighbour_lib(), "nb_neighbour_lists_" + self._suffix)
+        check(fn(self._device(positions, self._pos, (self.num_bodies, 4)), self.num_bodies, radius, radii, self._offsets.ptr,
+                 self._indices.ptr if capacity > 0 else None, capacity, self._status.ptr, self._workspace.ptr, self._workspace_bytes, stream), "nb_neighbour_lists")
+
+    def status(self, stream=None) -> dict:
+        out = NeighbourStatus()
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+        check(lib().nb_d2h(ctypes.byref(out), self._status.ptr, ctypes.sizeof(out), stream), "nb_d2h(status)")
+        return neighbour_status_dict(out)
+
+    def survey(self, positions, radius_sq=None, radii_sq=None, potentials=False, stream=None) -> dict:
+        self.enqueue_survey(positions, radius_sq, radii_sq, potentials, stream)
+        n = self.num_bodies
+        out = {"status": self.status(stream)}
+        out["nearest_index"] = self._nearest.download(np.empty(n, dtype=np.uint32))
+        out["nearest_dist_sq"] = self._nearest_d2.download(np.empty(n, dtype=self.dtype))
+        out["counts"] = self._counts.download(np.empty(n, dtype=np.uint32))
+        out["potentials"] = self._potentials.download(np.empty(n, dtype=self.dtype)) if potentials else None
+        return out
+
+    def lists(self, positions, radius_sq=None, radii_sq=None, capacity: int = 0, stream=None) -> dict:
+        """offsets (N + 1), indices (the total's entries; None when they exceed `capacity`: status['total_neighbours'] says what is needed)"""
+        self.enqueue_lists(positions, radius_sq, radii_sq, capacity, stream)
+        out = {"status": self.status(stream)}
+        out["offsets"] = self._offsets.download(np.empty(self.num_bodies + 1, dtype=np.uint64))
+        total = out["status"]["total_neighbours"]
+        if out["status"]["flags"] & NEIGHBOUR_OVERFLOW:
+            out["indices"] = None
+        else:
+            out["indices"] = self._indices.download(np.empty(total, dtype=np.uint32)) if total > 0 else np.empty(0, dtype=np.uint32)
+        return out
+
+    @property
+    def nearest_index_ptr(self):
+        return self._nearest.ptr
+
+    @property
+    def nearest_dist_sq_ptr(self):
+        return self._nearest_d2.ptr
+
+    @property
+    def counts_ptr(self):
+        return self._counts.ptr
+
+    @property
+    def potentials_ptr(self):
+        return self._potentials.ptr
+
+    @property
+    def status_ptr(self):
+        return self._status.ptr
 
     def free(self) -> None:
         for b in self._buffers():

@@ -4,6 +4,7 @@
 #include "bodysystemhip_hermite.hpp"
 #include "bodysystemhip_hermite_block.hpp"
 #include "compute.hpp"
+#include "neighbour_cli.hpp"
 #include "randomise_bodies.hpp"
 #include "text.hpp"
 
@@ -95,6 +96,12 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
         print_energy("energy end (" + std::to_string(intervals) + " steps)", end);
         std::printf(" relative_drift=%.9g\n", (end.total - start.total) / std::abs(start.total));
     };
+    const auto report_neighbourhood = [&]() {  // (of the synchronised snapshot)
+        if (run.neighbours < 0) return;
+        system.sync();
+        system.get_positions(pos);
+        report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
+    };
     if (run.benchmark) {
         const auto warm = system.advance(dt_max);  // (untimed, as Compute::run_benchmark)
         HipEvent   begin, stop;
@@ -109,6 +116,7 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
         report("= ", warm, end);
         std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
         report_energy(1 + static_cast<std::size_t>(run.iterations));
+        report_neighbourhood();
         return;
     }
     const auto none = system.status();
@@ -121,6 +129,7 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
     }
     report("", none, end);
     report_energy(run.steps);
+    report_neighbourhood();
 }
 
 template <typename T> auto run_typed(const HermiteRun& run) -> void {
@@ -143,6 +152,11 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         print_energy("energy end (" + std::to_string(steps) + " steps)", end);
         std::printf(" relative_drift=%.9g\n", (end.total - start.total) / std::abs(start.total));
     };
+    const auto report_neighbourhood = [&]() {
+        if (run.neighbours < 0) return;
+        system.get_positions(pos);
+        report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
+    };
     if (run.benchmark) {
         system.update(dt);  // (untimed, as Compute::run_benchmark)
         HipEvent begin, stop;
@@ -162,6 +176,7 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         std::printf("= %s %s-precision GFLOP/s at %d flops per acceleration + jerk interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
                     sizeof(T) == 8 ? "double" : "single", flops);
         report_energy(1 + static_cast<std::size_t>(run.iterations));
+        report_neighbourhood();
         return;
     }
     for (std::size_t s = 0; s < run.steps; ++s) system.update(dt);
@@ -171,6 +186,7 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         write_dump<T>(run, pos, vel);
     }
     report_energy(run.steps);
+    report_neighbourhood();
 }
 
 }  // namespace

@@ -17,6 +17,7 @@ struct HermiteRun {
     std::size_t           steps = 0;
     std::filesystem::path dump;
     bool                  energy = false;
+    double                neighbours = -1.0;  // --neighbours=<radius> (< 0: not asked for): report_neighbours of the final state
     bool                  block = false;  // --integrator=hermite-block: dt_max = the demo row's dt, `steps` / `iterations` count intervals of dt_max
     double                eta = 0.02;     // --eta (the first steps use eta_start = 0.01)
     int                   levels = 30;    // --levels: steps down to dt_max * 2^-levels

@@ -6,7 +6,7 @@
 //                     --tipsy=<file> -i,--iterations=<n> --blockSize=<n>      (single-dash spellings accepted too)
 //   extensions      : --numdevices=<n> | --devices=<list> (the NVIDIA sample's -numdevices, which this fork of it dropped)
 //                     --mode=fast|strict  --config=shell|random|expand  --demo=<0..6>  --steps=<n>  --dump=<file>
-//                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
+//                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --neighbours=<radius>  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
@@ -14,8 +14,10 @@
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
 #include "../../include/nbody_hip_hermite_block.h"
+#include "../../include/nbody_hip_neighbour.h"
 #include "compute.hpp"
 #include "integrate_nbody_hip.hpp"
+#include "neighbour_cli.hpp"
 
 #include <dlfcn.h>  // (the --alloc-limit-mib test hook lives in the lab library: looked up, never linked)
 
@@ -60,6 +62,7 @@ struct Options {
     bool                  graph = false;
     bool                  no_workspace = false;
     bool                  energy = false;  // print the energy at the start and the end of a --benchmark / --steps run
+    std::optional<double> neighbours;  // --neighbours=<radius>: after the run, the closest pair, the neighbour counts within the radius, the deepest potential
     std::size_t           workspace_mib = 0;  // 0: no bound of our own
     std::size_t           alloc_limit_mib = 0;  // test hook: device allocations above this are refused (0: none)
     std::vector<int>      devices;  // --numdevices=<n> (devices 0..n-1) or --devices=<a,b,...>: bodies sharded over several GPUs
@@ -104,6 +107,9 @@ Options:
                               one region of reaction planes; default: what the library asks for, at most a third of the device's memory)
   --energy                    With --benchmark or --steps: print the kinetic, potential and total energy and the momentum before and
                               after the run, and the relative drift of the total energy (one device only)
+  --neighbours FLOAT          After a --benchmark, --steps or --dump run: print the closest pair of bodies and its separation, the mean and
+                              the largest number of neighbours within this radius (>= 0) and its body, the deepest potential and its
+                              body (one device only, at most 16777216 bodies; accepted wherever --energy is)
   --inject-error FLOAT        Test hook: added to body 0's x of the fast result before --compare checks it
   --systems UINT              Step this many independent systems of --numbodies (<= 65536, required) bodies in one launch: system 0
                               is the single-system start-up state, the others the next draws; --benchmark counts B*N^2 interactions
@@ -266,6 +272,17 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
                 if (!ok) return error("--eta: Value not in range (0, 1]");
                 options.eta = eta;
             }
+        } else if (name == "neighbours") {
+            const auto v = take_value();
+            ok           = v.has_value();
+            if (ok) {
+                char*      end    = nullptr;
+                const auto text   = std::string(*v);
+                const auto radius = std::strtod(text.c_str(), &end);
+                ok                = end != nullptr && *end == '\0' && end != text.c_str() && std::isfinite(radius) && radius >= 0.0;
+                if (!ok) return error("--neighbours: Value not a radius (a finite number >= 0)");
+                options.neighbours = radius;
+            }
         } else if (name == "levels") {
             const auto v = take_value();
             int        l = 0;
@@ -286,13 +303,17 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
     if (options.energy && options.devices.size() > 1) return error("--energy is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
     if (options.energy && (options.compare || options.qatest)) return error("--energy cannot be combined with --compare or --qatest (those runs step two systems)");
 
+    if (options.neighbours && options.devices.size() > 1) return error("--neighbours is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
+    if (options.neighbours && (options.compare || options.qatest)) return error("--neighbours cannot be combined with --compare or --qatest (those runs step two systems)");
+    if (options.neighbours && options.numbodies > NB_NEIGHBOUR_MAX_BODIES) return error("--neighbours: --numbodies must be at most 16777216");
+
     if (options.systems > 0) {
         if (options.numbodies == 0) return error("--systems needs an explicit --numbodies of at most 65536 (the single-system default, blockSize * 4 * CUs, is above the ensemble limit)");
         if (options.numbodies > 65536) return error("--systems: --numbodies must be at most 65536 (above that one system fills the GPU: run it without --systems)");
         if (options.numbodies * options.systems > (std::size_t{1} << 31)) return error("--systems: numbodies * systems must be at most 2^31");
         if (options.devices.size() > 1) return error("--systems is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
-        if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.energy || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
-            return error("--systems cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --energy, --no-workspace, --workspace-mib or --cpu");
+        if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.energy || options.neighbours || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
+            return error("--systems cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --energy, --neighbours, --no-workspace, --workspace-mib or --cpu");
         }
     }
 
@@ -379,6 +400,7 @@ auto main(int argc, char** argv) -> int {
             run.steps      = cmd_options.steps;
             run.dump       = cmd_options.dump;
             run.energy     = cmd_options.energy;
+            run.neighbours = cmd_options.neighbours.value_or(-1.0);
             run.block      = cmd_options.hermite_block;
             run.eta        = cmd_options.eta.value_or(run.eta);
             run.levels     = cmd_options.levels.value_or(run.levels);
@@ -408,10 +430,21 @@ auto main(int argc, char** argv) -> int {
             print_energy(label.c_str(), end);
             std::printf(" relative_drift=%.9g\n", (end.total - energy_start->total) / std::abs(energy_start->total));
         };
+        // ... and then the neighbourhood of the final state (softened as the run)
+        const auto report_neighbourhood = [&]() {
+            if (!cmd_options.neighbours) return;
+            const auto softening = compute.active_params().softening;
+            if (compute.fp64_enabled()) {
+                report_neighbours(compute.positions_fp64(), *cmd_options.neighbours, static_cast<double>(softening) * static_cast<double>(softening));
+            } else {
+                report_neighbours(compute.positions_fp32(), *cmd_options.neighbours, softening * softening);
+            }
+        };
         if (cmd_options.benchmark) {
             const auto nb_iterations = cmd_options.iterations == 0 ? 10 : static_cast<int>(cmd_options.iterations);
             compute.run_benchmark(nb_iterations);
             report_energy(1 + static_cast<std::size_t>(nb_iterations));  // (run_benchmark takes one untimed step first)
+            report_neighbourhood();
             return 0;
         }
         if (compare_to_cpu) {
@@ -428,6 +461,7 @@ auto main(int argc, char** argv) -> int {
             }
         }
         report_energy(cmd_options.steps);
+        report_neighbourhood();
         return 0;
     } catch (const std::invalid_argument& e) {
         std::fprintf(stderr, "ERROR: %s\n", e.what());
