@@ -1,0 +1,287 @@
+"""The kernel matrix: every __global__ function the nine listings of `make -C cuda-nbody_amd/csrc asm` hold, and what checks it.
+
+Three lists, which together must equal the set of `.amdhsa_kernel` symbols (tests/test_kernel_matrix.py asserts it in both directions):
+
+  CASES        the shape-dispatched families -- a kernel picked from a family of template instantiations by N or by a plan.  A case
+               names the instantiation it claims (template arguments), the public entry point that reaches it, the override that
+               forces it (where one is needed), the shape, and the plan fields that select it as the plan QUERY reports them.  The GPU
+               part of tests/test_kernel_matrix.py runs every case and first asserts that the query, read on that device, selects the
+               claimed instantiation.
+  OTHER        every other kernel (schedule, scan, reduce, finish, predict, STRICT, pair_forces_clocked), once, with the existing test
+               that checks it.
+  UNREACHABLE  instantiations no public call can launch, each with the host-side reason, which is asserted.  None of them can be
+               selected by a default plan (no override) for any N: that is asserted too.
+
+A plain helper module: no fixture, no pytest setting.  Kernels are identified as (function name, template arguments), the arguments parsed
+from the mangled symbol with a regex (as tests/test_ensemble.py does); `c++filt` is only asked when that regex does not match."""
+import re
+import subprocess
+from dataclasses import dataclass
+
+import numpy as np
+
+F32, F64 = np.float32, np.float64
+TYPE_NAME = {F32: "float", F64: "double"}
+DTYPE_OF = {"float": F32, "double": F64}
+LANE_WIDTH = {F32: 2, F64: 1}  # W: bodies i per vector (fp32 travels in packed pairs)
+
+LISTINGS = ("nbody_fast.s", "nbody_strict.s", "nbody_pair.s", "nbody_energy.s", "ensemble_fast.s", "ensemble_strict.s", "hermite_eval.s", "hermite_block.s",
+            "neighbour.s")
+
+# ---------------------------------------------------------------------------------------------------------------- symbols
+_PREFIX = re.compile(r"^_ZN2nb12_GLOBAL__N_1(\d+)")
+_TEMPLATE = re.compile(r"^I([fd])((?:L[ib]\d+E)*)E")
+_ARGUMENT = re.compile(r"L([ib])(\d+)E")
+_DEMANGLED = re.compile(r"nb::\(anonymous namespace\)::(\w+)(?:<([^>]*)>)?\(")
+
+
+def parse_symbol(symbol):
+    """(function name, template arguments) of a kernel symbol: ("integrate_bodies_fast", ("float", 2, 8, 4)), ("block_scan", ())"""
+    m = _PREFIX.match(symbol)
+    if m:
+        start, length = m.end(), int(m.group(1))
+        name, rest = symbol[start:start + length], symbol[start + length:]
+        t = _TEMPLATE.match(rest)
+        if t:
+            args = [TYPE_NAME[F32 if t.group(1) == "f" else F64]]
+            args += [bool(int(v)) if k == "b" else int(v) for k, v in _ARGUMENT.findall(t.group(2))]
+            return name, tuple(args)
+        if rest.startswith("E"):
+            return name, ()
+    # fallback: the demangler's text, read with a regex of the same meaning
+    kernel = parse_demangled(subprocess.run(["c++filt", symbol], capture_output=True, text=True, check=True).stdout)
+    if kernel is None:
+        raise ValueError(f"cannot read the kernel symbol {symbol!r}")
+    return kernel
+
+
+def parse_demangled(text):
+    """the same from a demangled name, "void nb::(anonymous namespace)::hermite_eval<float, 4, false>(nb::HermiteArgs<float>)"; None if it is not one"""
+    d = _DEMANGLED.search(text)
+    if d is None:
+        return None
+    args = []
+    for a in (d.group(2) or "").split(","):
+        a = a.strip()
+        if a in ("float", "double"):
+            args.append(a)
+        elif a in ("true", "false"):
+            args.append(a == "true")
+        elif a:
+            args.append(int(re.sub(r"^\(\w+\)", "", a)))
+    return d.group(1), tuple(args)
+
+
+def kernel_name(kernel):
+    name, args = kernel
+    if not args:
+        return name
+    return name + "<" + ", ".join(("true" if a else "false") if isinstance(a, bool) else str(a) for a in args) + ">"
+
+
+def listed_kernels(text):
+    """the kernels of one listing: every `.amdhsa_kernel` symbol, parsed"""
+    return [parse_symbol(s) for s in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- cases
+@dataclass(frozen=True)
+class Case:
+    family: str        # the kernel's function name
+    dtype: type        # np.float32 / np.float64
+    args: tuple        # the template arguments after T
+    entry: str         # the public entry point that launches it
+    override: tuple    # (setter of the package, arguments) or ()
+    plan: tuple        # ((field of the plan query, value), ...): what selects the instantiation
+    shape: tuple = ()  # ((name, value), ...): N, or how the ranges are sized
+    note: str = ""
+
+    @property
+    def kernel(self):
+        return self.family, (TYPE_NAME[self.dtype], *self.args)
+
+    @property
+    def id(self):
+        shape = "".join(f" {k}={v}" for k, v in self.shape if k in ("n", "systems"))
+        return kernel_name(self.kernel).replace(" ", "") + shape
+
+
+# The wave-stream kernel: integrate_bodies_fast<T, R, S, LPT>.  R vectors of bodies i per lane (I = R W), S waves split j, chunks of
+# 64 LPT bodies j per wave.  nb_set_plan_override(I, S, tile) with tile = 64 S LPT forces each one; plan_fast reports them back as
+# bodies_per_lane, lanes_per_body, tile_bodies.  The ranges of a case are sized from (I, S, LPT) by test_kernel_matrix.stream_launches.
+def _stream_cases():
+    out = []
+    for dtype in (F32, F64):
+        w = LANE_WIDTH[dtype]
+        for r in ((1, 2) if dtype == F32 else (1, 2, 4)):
+            for s in (4, 8, 16):
+                for lpt in (1, 2, 4):
+                    if (s, lpt) == (16, 4):
+                        continue  # UNREACHABLE, below
+                    i, tile = r * w, 64 * s * lpt
+                    out.append(Case("integrate_bodies_fast", dtype, (r, s, lpt), "nb_integrate_shard", ("set_plan_override", (i, s, tile)),
+                                    (("bodies_per_lane", i), ("lanes_per_body", s), ("tile_bodies", tile), ("block_threads", 64 * s))))
+    return out
+
+
+# The wave-split kernel: integrate_bodies_wavesplit<T, R, LPT, BLOCK>.  A wave owns I = R W bodies i, a workgroup of BLOCK threads stages
+# tiles of LPT BLOCK bodies j.  nb_set_plan_override(I, 64, tile) fixes I and the tile; the workgroup size is plan_fast's own choice from
+# i_count and the device's CU count, so a case offers i_counts in units of the CU count and takes the first the query answers with its
+# BLOCK ("cu_multiples": i_count = CUs x multiple + 29; 0: a small range, 301 bodies).
+WAVESPLIT_FORMS = ((2, 256), (4, 256), (1, 512), (2, 512), (1, 1024))  # (LPT, BLOCK), the switch of dispatch_wavesplit
+
+
+def _wavesplit_cases():
+    out = []
+    for dtype in (F32, F64):
+        w = LANE_WIDTH[dtype]
+        for r in (1, 2):
+            for lpt, block in WAVESPLIT_FORMS:
+                i, tile = r * w, lpt * block
+                waves = block // 64
+                multiples = (0,) if block == 256 else tuple(k * i for k in (waves, waves * 3 // 2, waves // 2 * 3 // 2, waves // 2, waves * 2, waves * 3))
+                out.append(Case("integrate_bodies_wavesplit", dtype, (r, lpt, block), "nb_integrate_shard", ("set_plan_override", (i, 64, tile)),
+                                (("bodies_per_lane", i), ("lanes_per_body", 64), ("tile_bodies", tile), ("block_threads", block)),
+                                (("cu_multiples", multiples),)))
+    return out
+
+
+# The pairwise kernel: pair_forces<T, R, S>.  nb_set_pair_plan_override(R, S, splits, min_bodies = 1) forces each one at any size; the
+# query reports bodies_per_lane = R W and waves_per_block = S.  Whole systems of a ragged N step through nb_integrate_ws_*.
+PAIR_N = 3000  # fp32: 24 / 12 / 6 / 3 blocks (R = 1, 2, 4, 8); fp64: 47 / 24 / 12 / 6; the last block partly empty every time
+
+
+def _pair_cases():
+    out = []
+    for dtype in (F32, F64):
+        for r in (1, 2, 4, 8):
+            for s in (4, 8, 12, 16):
+                if (r, s) == (8, 16):
+                    continue  # UNREACHABLE, below
+                out.append(Case("pair_forces", dtype, (r, s), "nb_integrate_ws", ("set_pair_plan_override", (r, s, 2, 1)),
+                                (("applies", 1), ("slices", 1), ("bodies_per_lane", r * LANE_WIDTH[dtype]), ("waves_per_block", s)), (("n", PAIR_N),)))
+    return out
+
+
+# The libraries dispatched by N alone: S, the waves that split j, is 1 below 256 bodies, 2 from 256, 4 from 512, 8 from 1 024
+# (plan_ensemble_fast, plan_hermite, block_waves, neighbour_waves).  The sizes sit on and around every switch point -- a wave gets exactly
+# one chunk, then one chunk and one ragged body -- and inside the S = 4 window.
+N_BY_WAVES = {1: (255,), 2: (256, 257, 511), 4: (512, 513, 700, 1023), 8: (1024, 1025)}
+MASSES = ("equal", "species", "random")
+ENSEMBLE_LARGE = ((8192 + 37, 3), (65536, 2))  # (bodies, systems), S = 8: the fp32 second-level sums fire from 8 192 bodies; the API's largest N
+
+
+def ensemble_vectors(dtype, waves):
+    """R of ensemble_fast<T, R, S>: I = min(S, 4) bodies i per lane, at least one vector"""
+    return max(min(waves, 4), LANE_WIDTH[dtype]) // LANE_WIDTH[dtype]
+
+
+def _n_dispatched_cases():
+    out = []
+    for dtype in (F32, F64):
+        w = LANE_WIDTH[dtype]
+        for s, sizes in N_BY_WAVES.items():
+            r = ensemble_vectors(dtype, s)
+            for n, systems in [(n, 3) for n in sizes] + (list(ENSEMBLE_LARGE) if s == 8 else []):
+                out.append(Case("ensemble_fast", dtype, (r, s), "nb_ensemble_integrate", (), (("bodies_per_lane", r * w), ("waves_per_group", s)),
+                                (("n", n), ("systems", systems))))
+            for n in sizes:
+                for step in (False, True):
+                    out.append(Case("hermite_eval", dtype, (s, step), "nb_hermite_step" if step else "nb_hermite_eval", (), (("waves_per_group", s),), (("n", n),)))
+                out.append(Case("hermite_block_eval", dtype, (s,), "nb_hermite_block_step", (), (("waves_per_group", s),), (("n", n),)))
+                for pot in (False, True):
+                    out.append(Case("neighbour_survey", dtype, (s, pot), "nb_neighbour_survey", (), (("waves_per_group", s),), (("n", n),),
+                                    "POT = false: the survey of distances and counts (and the lists built on it); true: with potentials"))
+    return out
+
+
+CASES = _stream_cases() + _wavesplit_cases() + _pair_cases() + _n_dispatched_cases()
+FAMILIES = ("integrate_bodies_fast", "integrate_bodies_wavesplit", "pair_forces", "ensemble_fast", "hermite_eval", "hermite_block_eval", "neighbour_survey")
+
+
+def cases_of(family):
+    return [c for c in CASES if c.family == family]
+
+
+def claimed_kernels():
+    return {c.kernel for c in CASES}
+
+
+# ---------------------------------------------------------------------------------------------------------------- every other kernel
+def _both(name, test):
+    return {(name, ("float",)): test, (name, ("double",)): test}
+
+
+OTHER = {
+    **_both("integrate_bodies_strict", "tests.test_gpu_parity::test_strict_matches_oracle_bitwise_ragged"),
+    **_both("ensemble_strict", "tests.test_ensemble::test_strict_every_system_matches_the_oracle"),
+    **_both("energy_pairs", "tests.test_energy::test_energy_matches_fp64_numpy"),
+    ("energy_finish", ()): "tests.test_energy::test_energy_matches_fp64_numpy",
+    **_both("pair_finish", "tests.test_pairwise::test_pair_mass_forms"),
+    **_both("pair_reduce", "tests.test_pairwise::test_sliced_pairwise_force_error"),
+    ("pair_forces_clocked", ("float", 8, 8)): "tests.test_pairwise::test_clocked_variant_of_the_forces_kernel_changes_no_bit",
+    ("pair_forces_clocked", ("double", 8, 8)): "tests.test_pairwise::test_clocked_variant_of_the_forces_kernel_changes_no_bit",
+    **_both("hermite_predict", "tests.test_hermite::test_one_step_against_long_double"),
+    **_both("hermite_timestep_partial", "tests.test_hermite::test_shared_time_step"),
+    **_both("hermite_timestep_final", "tests.test_hermite::test_shared_time_step"),
+    ("block_min_partial", ()): "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double",
+    **_both("block_predict_count", "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double"),
+    ("block_scan", ()): "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double",
+    ("block_scatter", ()): "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double",
+    **_both("hermite_block_finish", "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double"),
+    **_both("block_init_levels", "tests.test_hermite_block::test_init_levels_against_long_double"),
+    **_both("block_sync", "tests.test_hermite_block::test_python_class_gives_the_c_calls_bits"),
+    ("neighbour_status", ()): "tests.test_neighbour::test_exact_lattices",
+    **_both("neighbour_count", "tests.test_neighbour::test_exact_lattices"),
+    ("list_block", ()): "tests.test_neighbour::test_exact_lattices",
+    ("list_scan", ()): "tests.test_neighbour::test_exact_lattices",
+    ("list_offsets", ()): "tests.test_neighbour::test_exact_lattices",
+    **_both("neighbour_fill", "tests.test_neighbour::test_exact_lattices"),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------- unreachable
+GFX950_LDS_BYTES = 160 * 1024  # the LDS of one CU, the most a workgroup can be given (kPairLdsLimit, nbody_kernels.h)
+
+
+@dataclass(frozen=True)
+class Unreachable:
+    kernel: tuple
+    kind: str      # which host-side reason test_kernel_matrix.test_unreachable_reasons_hold asserts
+    reason: str
+    override: tuple  # what a caller would have to set to ask for it
+
+
+PAIR_SIZES = (129, 517, 3000, 4160, 8193, 20000, 65536, 262144, 1048576)
+
+# pair_forces<T, 8, 16>: sixteen waves each folding 3 x 8 vectors of 64 W-wide lanes need 16 * 3 * 8 * W * 64 * sizeof(T) + 256 = 196 864
+# bytes of LDS in either precision, whatever N and however the units are dealt (pair_lds_bytes with no tail sums) -- more than a CU has, so
+# the runtime refuses the launch and the step reports the error.  The default plan never asks for it: S is 8 unless the override sets it.
+#
+# integrate_bodies_fast<T, R, 16, 4>: sixteen waves with chunks of 256 bodies j are tile_bodies = 4 096.  plan_fast itself gives sixteen
+# waves 128 bodies each (2 048), and nb_set_plan_override takes no tile above 2 048 (NB_ERR_INVALID_ARGUMENT, the previous override stays).
+UNREACHABLE = [
+    Unreachable(("pair_forces", (TYPE_NAME[dtype], 8, 16)), "pair_lds",
+                "needs 196 864 bytes of LDS per workgroup for every N: more than the 160 KiB of a gfx950 CU; default plans keep S = 8",
+                ("set_pair_plan_override", (8, 16, 1, 1)))
+    for dtype in (F32, F64)
+] + [
+    Unreachable(("integrate_bodies_fast", (TYPE_NAME[dtype], r, 16, 4)), "tile_refused",
+                "tile_bodies = 4 096: nb_set_plan_override refuses it, and plan_fast gives 16 waves tiles of 2 048 bodies",
+                ("set_plan_override", (r * LANE_WIDTH[dtype], 16, 4096)))
+    for dtype in (F32, F64) for r in ((1, 2) if dtype == F32 else (1, 2, 4))
+]
+
+
+def registry():
+    """kernel -> what the registry says about it; raises if a kernel is named twice"""
+    out = {}
+    for kernel in sorted(claimed_kernels()):
+        out[kernel] = "cases"
+    for kernel in OTHER:
+        assert kernel not in out, kernel_name(kernel)
+        out[kernel] = "other"
+    for u in UNREACHABLE:
+        assert u.kernel not in out, kernel_name(u.kernel)
+        out[u.kernel] = "unreachable"
+    return out

@@ -446,22 +446,27 @@ def ld_step(pos, vel, acc, jerk, dt, eps2, predicted):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_one_step_against_long_double(gpu, dtype):
     for n, mass, eps2, dt in ((1, "equal", 0.01, 0.01), (65, "random", 0.01, 0.01), (1000, "equal", 0.01, 1.0 / 64), (1000, "species", 1e-4, 1e-3), (2085, "equal", 0.01, -0.01)):
-        pos, vel = cloud(n, dtype, 31 + n, mass)
-        eps2, dt = dtype(eps2), dtype(dt)
-        d = Device(gpu, pos, vel, eps2)
-        d.eval()
-        acc, jerk = d.get("acc"), d.get("jerk")
-        d.step(dt, new="pos2", old="pos")
-        got, predicted = d.state("pos2"), d.get("ws")
-        d.free()
-        want, bounds = ld_step(pos, vel, acc, jerk, dt, eps2, predicted)
-        for name, g, w, b in zip(("position", "velocity", "acceleration", "jerk"), got, want, bounds):
-            err = np.abs(g[:, :3].astype(LD) - w)
-            with np.errstate(all="ignore"):
-                print(f"n {n} {mass} dt {dt}: {name} at {float(np.nanmax(np.where(b > 0, err / b, 0))):.3g} of its bound")
-            assert (err <= b).all(), (n, mass, name)
-        assert got[0][:, 3].tobytes() == pos[:, 3].tobytes() and got[1][:, 3].tobytes() == vel[:, 3].tobytes()
-        assert not got[2][:, 3].any() and not got[3][:, 3].any()
+        check_one_step(gpu, dtype, n, mass, eps2, dt)
+
+
+def check_one_step(gpu, dtype, n, mass, eps2, dt):
+    """an evaluation and one step of cloud(n, mass) against ld_step, stage by stage; shared with tests/test_kernel_matrix.py"""
+    pos, vel = cloud(n, dtype, 31 + n, mass)
+    eps2, dt = dtype(eps2), dtype(dt)
+    d = Device(gpu, pos, vel, eps2)
+    d.eval()
+    acc, jerk = d.get("acc"), d.get("jerk")
+    d.step(dt, new="pos2", old="pos")
+    got, predicted = d.state("pos2"), d.get("ws")
+    d.free()
+    want, bounds = ld_step(pos, vel, acc, jerk, dt, eps2, predicted)
+    for name, g, w, b in zip(("position", "velocity", "acceleration", "jerk"), got, want, bounds):
+        err = np.abs(g[:, :3].astype(LD) - w)
+        with np.errstate(all="ignore"):
+            print(f"n {n} {mass} dt {dt}: {name} at {float(np.nanmax(np.where(b > 0, err / b, 0))):.3g} of its bound")
+        assert (err <= b).all(), (n, mass, name)
+    assert got[0][:, 3].tobytes() == pos[:, 3].tobytes() and got[1][:, 3].tobytes() == vel[:, 3].tobytes()
+    assert not got[2][:, 3].any() and not got[3][:, 3].any()
 
 
 def run(gpu, pos, vel, eps2, dt, steps):

@@ -528,12 +528,17 @@ _DECISIONS = {"checked": 0, "near": 0, "closest": np.inf}
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("n,n_act", STAGE_CASES)
 def test_one_block_step_stage_by_stage_against_long_double(gpu, dtype, n, n_act):
-    tol, u = LD(TOL[dtype]), LD(UNIT_ROUNDOFF[dtype])
     mass = ("equal", "species", "random")[(n + n_act) % 3]
+    eta = (2e-5, 3e-4, 4e-3, 0.05)[STAGE_CASES.index((n, n_act)) % 4]  # (decisions in both directions: dt_A ~ sqrt(eta) x the bodies' time scale against steps of 2^-11 .. 2^-8)
+    check_block_stages(gpu, dtype, n, n_act, mass, eta)
+
+
+def check_block_stages(gpu, dtype, n, n_act, mass, eta):
+    """one block step of n_act due bodies among n (hand_made_schedule), every stage against long double; shared with tests/test_kernel_matrix.py"""
+    tol, u = LD(TOL[dtype]), LD(UNIT_ROUNDOFF[dtype])
     pos, vel = cloud(n, dtype, 1000 + n + n_act, mass)
     eps2 = dtype(0.01)
     now, max_level, active, levels, ticks = hand_made_schedule(n, n_act, n * 7 + n_act)
-    eta = (2e-5, 3e-4, 4e-3, 0.05)[STAGE_CASES.index((n, n_act)) % 4]  # (decisions in both directions: dt_A ~ sqrt(eta) x the bodies' time scale against steps of 2^-11 .. 2^-8)
     params = gpu.HermiteBlockParams(eta, 0.01, 0.125, max_level, 0)
     q = 0.125 * 2.0 ** -max_level
     acc, jerk = hermite_eval(gpu, pos, vel, eps2)
