@@ -34,6 +34,8 @@ HERMITE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_LIB", os.path.join(HERE, "l
 HERMITE_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_LIB", os.path.join(HERE, "libnbody_hip_hermite_block.so"))
 # Nearest neighbours, potentials and neighbour lists (include/nbody_hip_neighbour.h) are a sixth, loaded by neighbour_lib().
 NEIGHBOUR_LIB_PATH = os.environ.get("NBODY_HIP_NEIGHBOUR_LIB", os.path.join(HERE, "libnbody_hip_neighbour.so"))
+# Acceleration, jerk and potential of N sources at M points of the caller's own (include/nbody_hip_field.h) are a seventh, loaded by field_lib().
+FIELD_LIB_PATH = os.environ.get("NBODY_HIP_FIELD_LIB", os.path.join(HERE, "libnbody_hip_field.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -324,8 +326,29 @@ NEIGHBOUR_SIGNATURES = {
     "nb_neighbour_lists_f64": (_ci, [_vp, _cu, _cd, _vp, _vp, _vp, _ull, _vp, _vp, _sz, _vp]),
 }
 
+
+# include/nbody_hip_field.h: exported by libnbody_hip_field.so, and nothing else is
+class FieldPlan(ctypes.Structure):
+    """nb_field_plan_t: the geometry of an evaluation, a function of N, M and the precision"""
+    _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("unroll", _ci), ("tiles", _cu), ("ranges", _cu), ("groups", _cu), ("block_threads", _cu),
+                ("lds_bytes", _cu), ("launches", _cu), ("reserved", _cu), ("partial_offset", ctypes.c_ulonglong), ("partial_bytes", ctypes.c_ulonglong)]
+
+
+FIELD_MAX_SOURCES = 1 << 26
+FIELD_MAX_TARGETS = 1 << 24
+FIELD_NONE = 0xFFFFFFFF
+FIELD_SIGNATURES = {
+    "nb_field_workspace_bytes": (_ci, [_cu, _cu, _cu, _P(_sz)]),
+    "nb_field_plan_f32": (_ci, [_cu, _cu, _P(FieldPlan)]),
+    "nb_field_plan_f64": (_ci, [_cu, _cu, _P(FieldPlan)]),
+    # sources source_velocities N | targets target_velocities self_index M softening_sq | accelerations jerks potentials | workspace workspace_bytes stream
+    "nb_field_eval_f32": (_ci, [_vp, _vp, _cu, _vp, _vp, _vp, _cu, _cf, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nb_field_eval_f64": (_ci, [_vp, _vp, _cu, _vp, _vp, _vp, _cu, _cd, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 _neighbour_lib = None
+_field_lib = None
 _ensemble_lib = None
 _hermite_lib = None
 _hermite_block_lib = None
@@ -419,6 +442,21 @@ def neighbour_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _neighbour_lib = handle
     return _neighbour_lib
+
+
+def field_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_field.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _field_lib
+    if _field_lib is None:
+        if not os.path.exists(FIELD_LIB_PATH):
+            raise FileNotFoundError(f"{FIELD_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(FIELD_LIB_PATH)
+        for name, (restype, argtypes) in FIELD_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _field_lib = handle
+    return _field_lib
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -1066,6 +1104,115 @@ class NeighbourSurvey:
     @property
     def status_ptr(self):
         return self._status.ptr
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+def field_plan(num_sources: int, num_targets: int, dtype=np.float32) -> FieldPlan:
+    """nb_field_plan_*: the geometry of an evaluation of `num_sources` sources at `num_targets` points"""
+    p = FieldPlan()
+    fn = field_lib().nb_field_plan_f32 if np.dtype(dtype) == np.float32 else field_lib().nb_field_plan_f64
+    check(fn(num_sources, num_targets, ctypes.byref(p)), "nb_field_plan")
+    return p
+
+
+def field_workspace_bytes(num_sources: int, num_targets: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(field_lib().nb_field_workspace_bytes(num_sources, num_targets, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_field_workspace_bytes")
+    return out.value
+
+
+class FieldProbe:
+    """Acceleration, jerk and potential of N sources at up to `max_targets` points of the caller's own (include/nbody_hip_field.h).
+
+    The outputs, the workspace (sized for every M up to `max_targets`) and staging copies of the inputs are device buffers owned here.
+    ``sources`` / ``source_velocities`` are device addresses (a DeviceBuffer, its ``ptr`` or an int: T[4 N], only read) or host arrays of
+    shape (N, 4); ``targets`` / ``target_velocities`` likewise with (M, 4), ``self_index`` with (M,) of uint32.  A device address for
+    ``targets`` needs ``num_targets``.  ``eval`` enqueues on `stream`, waits for it and returns numpy arrays; ``enqueue`` only enqueues
+    (outputs stay on the device: see the ``*_ptr`` attributes)."""
+
+    def __init__(self, num_sources: int, max_targets: int, dtype=np.float32, softening_sq=0.0):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_sources, self.max_targets = n, m = int(num_sources), int(max_targets)
+        self.softening_sq = self.dtype.type(softening_sq)
+        size, per_tile = self.dtype.itemsize, 128 if self.dtype == np.float32 else 64
+        # the workspace of the largest call: the partial planes exist while tiles * J is short of the geometry's target, so the tile
+        # counts up to that target (and the largest M) cover every M; the query refuses the sizes the calls refuse
+        tiles_max = -(-m // per_tile)
+        sizes = {min(m, t * per_tile) for t in range(1, min(tiles_max, 1024) + 1)} | {m}
+        self._workspace_bytes = max(field_workspace_bytes(n, count, self.dtype) for count in sizes)
+        self._src, self._src_vel = DeviceBuffer(4 * n * size), DeviceBuffer(4 * n * size)
+        self._tgt, self._tgt_vel, self._self = DeviceBuffer(4 * m * size), DeviceBuffer(4 * m * size), DeviceBuffer(4 * m)
+        self._acc, self._jerk, self._pot = DeviceBuffer(4 * m * size), DeviceBuffer(4 * m * size), DeviceBuffer(m * size)
+        self._workspace = DeviceBuffer(max(self._workspace_bytes, 256))
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+
+    def _buffers(self):
+        return [self._src, self._src_vel, self._tgt, self._tgt_vel, self._self, self._acc, self._jerk, self._pot, self._workspace]
+
+    def _device(self, data, own: DeviceBuffer, shape, dtype=None):
+        """the device address of `data`: its own when it is one, else a host array uploaded into `own`"""
+        if data is None:
+            return None
+        if isinstance(data, DeviceBuffer):
+            return data.ptr
+        if isinstance(data, (int, ctypes.c_void_p)):
+            return data
+        host = np.ascontiguousarray(data, dtype=dtype or self.dtype)
+        if host.shape != shape:
+            raise ValueError(f"expected an array of shape {shape}, got {host.shape}")
+        own.upload(host)
+        return own.ptr
+
+    def enqueue(self, sources, targets, source_velocities=None, target_velocities=None, self_index=None, num_targets=None, accelerations=True, jerks=False,
+                potentials=True, stream=None) -> int:
+        """-> M.  `num_targets` is needed when `targets` is a device address, else it is the host array's length."""
+        if num_targets is None:
+            if isinstance(targets, (DeviceBuffer, int, ctypes.c_void_p)):
+                raise ValueError("targets given as a device address: say num_targets")
+            num_targets = np.shape(targets)[0]
+        m = int(num_targets)
+        if not 1 <= m <= self.max_targets:
+            raise ValueError(f"1 <= num_targets <= {self.max_targets}")
+        if jerks and (source_velocities is None or target_velocities is None):
+            raise ValueError("jerks need source_velocities and target_velocities")
+        n = self.num_sources
+        fn = getattr(field_lib(), "nb_field_eval_" + self._suffix)
+        check(fn(self._device(sources, self._src, (n, 4)), self._device(source_velocities, self._src_vel, (n, 4)), n, self._device(targets, self._tgt, (m, 4)),
+                 self._device(target_velocities, self._tgt_vel, (m, 4)), self._device(self_index, self._self, (m,), np.uint32), m, self._scalar(self.softening_sq),
+                 self._acc.ptr if accelerations else None, self._jerk.ptr if jerks else None, self._pot.ptr if potentials else None, self._workspace.ptr,
+                 self._workspace.nbytes, stream), "nb_field_eval")
+        return m
+
+    def eval(self, sources, targets, source_velocities=None, target_velocities=None, self_index=None, jerks=False, potentials=True, stream=None, num_targets=None) -> dict:
+        """accelerations (M, 4); jerks (M, 4) or None; potentials (M,) or None"""
+        m = self.enqueue(sources, targets, source_velocities, target_velocities, self_index, num_targets, True, jerks, potentials, stream)
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+        out = {"accelerations": self._acc.download(np.empty((m, 4), dtype=self.dtype))}
+        out["jerks"] = self._jerk.download(np.empty((m, 4), dtype=self.dtype)) if jerks else None
+        out["potentials"] = self._pot.download(np.empty(m, dtype=self.dtype)) if potentials else None
+        return out
+
+    @property
+    def accelerations_ptr(self):
+        return self._acc.ptr
+
+    @property
+    def jerks_ptr(self):
+        return self._jerk.ptr
+
+    @property
+    def potentials_ptr(self):
+        return self._pot.ptr
+
+    @property
+    def workspace_ptr(self):
+        return self._workspace.ptr
 
     def free(self) -> None:
         for b in self._buffers():

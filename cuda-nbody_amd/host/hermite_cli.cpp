@@ -4,6 +4,7 @@
 #include "bodysystemhip_hermite.hpp"
 #include "bodysystemhip_hermite_block.hpp"
 #include "compute.hpp"
+#include "field_cli.hpp"
 #include "neighbour_cli.hpp"
 #include "randomise_bodies.hpp"
 #include "text.hpp"
@@ -102,6 +103,12 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
         system.get_positions(pos);
         report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
     };
+    const auto report_field_points = [&]() {  // (of the synchronised snapshot)
+        if (run.field_points.empty()) return;
+        system.sync();
+        system.get_positions(pos);
+        report_field(std::span<const T>(pos), run.field_points, softening_sq);
+    };
     if (run.benchmark) {
         const auto warm = system.advance(dt_max);  // (untimed, as Compute::run_benchmark)
         HipEvent   begin, stop;
@@ -117,6 +124,7 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
         std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
         report_energy(1 + static_cast<std::size_t>(run.iterations));
         report_neighbourhood();
+        report_field_points();
         return;
     }
     const auto none = system.status();
@@ -130,6 +138,7 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
     report("", none, end);
     report_energy(run.steps);
     report_neighbourhood();
+    report_field_points();
 }
 
 template <typename T> auto run_typed(const HermiteRun& run) -> void {
@@ -157,6 +166,11 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         system.get_positions(pos);
         report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
     };
+    const auto report_field_points = [&]() {
+        if (run.field_points.empty()) return;
+        system.get_positions(pos);
+        report_field(std::span<const T>(pos), run.field_points, softening_sq);
+    };
     if (run.benchmark) {
         system.update(dt);  // (untimed, as Compute::run_benchmark)
         HipEvent begin, stop;
@@ -177,6 +191,7 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
                     sizeof(T) == 8 ? "double" : "single", flops);
         report_energy(1 + static_cast<std::size_t>(run.iterations));
         report_neighbourhood();
+        report_field_points();
         return;
     }
     for (std::size_t s = 0; s < run.steps; ++s) system.update(dt);
@@ -187,6 +202,7 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
     }
     report_energy(run.steps);
     report_neighbourhood();
+    report_field_points();
 }
 
 }  // namespace

@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <filesystem>
+#include <vector>
 
 struct HermiteRun {
     bool                  fp64 = false;
@@ -18,6 +19,7 @@ struct HermiteRun {
     std::filesystem::path dump;
     bool                  energy = false;
     double                neighbours = -1.0;  // --neighbours=<radius> (< 0: not asked for): report_neighbours of the final state
+    std::vector<double>   field_points;  // --field=<file>: x y z of every point (empty: not asked for): report_field of the final state
     bool                  block = false;  // --integrator=hermite-block: dt_max = the demo row's dt, `steps` / `iterations` count intervals of dt_max
     double                eta = 0.02;     // --eta (the first steps use eta_start = 0.01)
     int                   levels = 30;    // --levels: steps down to dt_max * 2^-levels
