@@ -1,12 +1,14 @@
 // field.hip -- the kernels of libnbody_hip_field.so (include/nbody_hip_field.h): acceleration, jerk and potential of N sources at M
 // points of the caller's own.  gfx950 only; FMA contraction on.
 //
-// field_eval<T, S, JERK> has the wave-stream plan of hermite_eval (a lane holds one vector of targets -- fp32: a packed pair ->
+// field_eval<T, S, JERK> is on the wave-stream plan (wave_stream.h: a lane holds one vector of targets -- fp32: a packed pair ->
 // v_pk_*_f32; fp64: one --, the sources are wave-uniform, come in through scalar loads U at a time, one group ahead, two register sets,
 // and enter the packed subtractions as scalar operands) with hermite_block_eval's division of work: a workgroup owns one tile of 64 W
 // targets and one of J contiguous ranges of the chunks of 128 sources; its S waves split the range's chunks (chunk c of the range ->
 // wave c mod S) and fold through LDS in wave order.  No LDS access and no barrier inside the streaming loops, no atomics anywhere, no
-// scratch, <= 128 VGPRs.
+// scratch, <= 128 VGPRs.  The streaming of a chunk's groups (wave_groups.inc), SIMD-mate priority (wave_mates.inc) and the fold
+// (wave_fold.inc) are the text hermite_stream.inc includes; the interaction and the chunk loop (mask form, no unit form) are this
+// kernel's own.  field_finish adds the J ranges' planes with hermite_block_finish's text (range_sum.inc).
 //
 // Per interaction, r = x_j - p, w = v_j - u, s2 = r.r + eps2, k = m_j s^-3:
 //     a += k r,   jerk += k (w - 3 (r.w) s^-2 r),   phi_sum += m_j s^-1        (phi = -phi_sum, at the store)
@@ -28,7 +30,6 @@ namespace {
 #include "nbody_lane.h"
 
 #include "hermite_stream.h"
-static_assert(kChunk == static_cast<int>(kFieldChunk), "the geometry counts hermite_stream.h's chunks");
 
 // s^-1, s^-2 and s^-3 from s2: hermite_stream.h's Powers and the first power beside them.  fp32: v_rsq_f32 (1 ulp) and two products; s^-1
 // is the v_rsq result itself.  fp64: s^-2 and s^-3 as Powers<double> (the v_rsq_f64 seed and the series of Lane<double>::coupling), and
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     for (int q = 0; q < NS; ++q) first[q] = second[q] = LT::splat(0);
 
     // the range's chunks: [c_lo, c_hi), never empty (J <= n_chunks / S)
-    const unsigned n_chunks = (n + CH - 1) / CH;
+    const unsigned n_chunks = stream_chunks(n);
     const unsigned c_lo     = static_cast<unsigned>(static_cast<unsigned long long>(range) * n_chunks / ranges);
     const unsigned c_hi     = static_cast<unsigned>(static_cast<unsigned long long>(range + 1) * n_chunks / ranges);
 
@@ -180,58 +181,22 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             if constexpr (JERK) sum[4] = LT::fma(ex[u], k3[u], sum[4]), sum[5] = LT::fma(ey[u], k3[u], sum[5]), sum[6] = LT::fma(ez[u], k3[u], sum[6]);
         }
     };
-    // a group of U sources in stage blocks of UB, as hermite_stream.inc: fp32 2 x 2, fp64 one block of 2
-    constexpr int UB = sizeof(T) == 8 ? U : U / 2;
-    auto whole = [&]<bool MASK>(const BodyJ<T> (&b)[U], unsigned j0) {
-#pragma unroll
-        for (int h = 0; h < U; h += UB) compute.template operator()<MASK, UB>(b + h, j0 + h, first);
-    };
-    auto arrived = [](const BodyJ<T> (&b)[U]) { asm volatile("" : : "s"(b[0].p) : "memory"); };  // what follows is issued after the set's wait
-    // b0 holds (or is loading) group 0 of the chunk at source `chunk`; on return it is loading the first group at source `next`
-    auto stream = [&]<bool MASK>(unsigned chunk, unsigned groups, size_t next, BodyJ<T> (&b0)[U], BodyJ<T> (&b1)[U]) {
-        unsigned g = 0;
-#pragma unroll 1
-        for (; g + 2 <= groups; g += 2) {
-            arrived(b0);
-            group(static_cast<size_t>(chunk) + (g + 1) * U, b1);
-            __builtin_amdgcn_sched_barrier(0);  // (the load stays ahead of the compute it overlaps)
-            whole.template operator()<MASK>(b0, chunk + g * U);
-            arrived(b1);
-            group(g + 2 < groups ? static_cast<size_t>(chunk) + (g + 2) * U : next, b0);
-            __builtin_amdgcn_sched_barrier(0);
-            whole.template operator()<MASK>(b1, chunk + (g + 1) * U);
-        }
-        if (g < groups) whole.template operator()<MASK>(b0, chunk + g * U);  // (odd count: the ragged last chunk, nothing follows it)
-    };
+#include "wave_groups.inc"
     auto flush = [&]() {
 #pragma unroll
         for (int q = 0; q < NS; ++q) second[q] = second[q] + first[q], first[q] = LT::splat(0);
     };
 
-    // SIMD-mate priority, as hermite_eval (plain LDS words, one writer each; no result bit depends on it)
-    __shared__ unsigned progress[4 * 8];
-    if (tid < 32) progress[tid] = 0xffffffffu;
-    __syncthreads();
-    const unsigned           simd = static_cast<unsigned>(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4));  // HW_REG_HW_ID[5:4] = SIMD_ID
-    volatile unsigned* const mine = progress + simd * 8;
-    unsigned                 done = 0;
-    if (lane == 0) mine[wave] = 0;
+#define WAVE_MATES_SETUP
+#include "wave_mates.inc"
 
     unsigned c    = c_lo + wave;  // wave w streams chunks c_lo + w, c_lo + w + S, ...
     unsigned held = 0;            // chunks in `first`
     BodyJ<T> b0[U], b1[U];
     if (c < c_hi && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
     for (; c < c_hi; c += S) {
-        if constexpr (S > 1) {
-            unsigned least = done;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) least = min(least, mine[q]);
-            if (static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(least))) >= done) {
-                __builtin_amdgcn_s_setprio(3);
-            } else {
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
+#define WAVE_MATES_CHUNK
+#include "wave_mates.inc"
         const unsigned first_j = c * CH;
         const unsigned count   = min(static_cast<unsigned>(CH), n - first_j);
         const unsigned groups  = count / U;
@@ -254,32 +219,14 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             compute.template operator()<true, 1>(one, first_j + jj, first);
         }
         ++held;
-        ++done;
-        if (lane == 0) mine[wave] = done;
+#define WAVE_MATES_DONE
+#include "wave_mates.inc"
     }
-    if (lane == 0) mine[wave] = 0xffffffffu;  // finished: never the one the others defer to
-    __builtin_amdgcn_s_setprio(0);
+#define WAVE_MATES_LEAVE
+#include "wave_mates.inc"
     flush();
 
-    // fold the S partial sums (waves 1..S-1 -> wave 0) through LDS, fixed order
-    __shared__ T red[(S > 1 ? S - 1 : 1) * NS * W * 64];
-    if (wave > 0) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) red[(((wave - 1) * NS + q) * W + k) * 64 + lane] = LT::get(second[q], k);
-        }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll 1
-    for (int g = 1; g < S; ++g) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) LT::set(second[q], k, LT::get(second[q], k) + red[(((g - 1) * NS + q) * W + k) * 64 + lane]);
-        }
-    }
+#include "wave_fold.inc"
 
     if (ranges > 1) {
         // planes [J][NS][slots]: word (range, q, slot), coalesced across the wave; the slots past M of the last tile hold a copy of the last target's sums
@@ -310,33 +257,15 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     }
 }
 
-// one lane per target: the J ranges' partial sums in range order, eight ranges' loads in flight at a time (hermite_block_finish)
+// one lane per target: the J ranges' partial sums in range order (range_sum.inc)
 template <typename T, bool JERK> __global__ __launch_bounds__(256) void field_finish(FieldArgs<T> a, unsigned ranges, unsigned tiles) {
     using vec4         = typename Lane<T>::vec4;
     constexpr int NS   = sums_of<JERK>();
     const unsigned slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= a.m) return;
     const size_t slots = static_cast<size_t>(tiles) * (64 * Lane<T>::W);
-    T            sum[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) sum[q] = a.partial[q * slots + slot];
-#pragma unroll 1
-    for (unsigned r0 = 1; r0 < ranges; r0 += 8) {
-        T part[8][NS];
-#pragma unroll
-        for (unsigned u = 0; u < 8; ++u) {
-            const size_t r = r0 + u < ranges ? r0 + u : r0;
-#pragma unroll
-            for (int q = 0; q < NS; ++q) part[u][q] = a.partial[(r * NS + q) * slots + slot];
-        }
-#pragma unroll
-        for (unsigned u = 0; u < 8; ++u) {
-            if (r0 + u < ranges) {
-#pragma unroll
-                for (int q = 0; q < NS; ++q) sum[q] += part[u][q];
-            }
-        }
-    }
+    const T* const partial = a.partial;
+#include "range_sum.inc"
     if (a.acc != nullptr) {
         vec4 a1;
         a1.x = sum[0], a1.y = sum[1], a1.z = sum[2], a1.w = 0;

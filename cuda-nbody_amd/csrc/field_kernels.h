@@ -4,12 +4,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "wave_stream.h"
+
 namespace nb {
 
 inline constexpr unsigned kFieldMaxSources = 1u << 26;
 inline constexpr unsigned kFieldMaxTargets = 1u << 24;
 inline constexpr unsigned kFieldNone       = 0xFFFFFFFFu;
-inline constexpr unsigned kFieldChunk      = 128;  // sources per wave and chunk (hermite_stream.h's)
 #ifndef NB_FIELD_TARGET
 #define NB_FIELD_TARGET 512  // (a sweep builds with other values: make EXP=-DNB_FIELD_TARGET=...)
 #endif
@@ -20,22 +21,10 @@ inline constexpr unsigned kFieldThreads = 256;              // block size of fie
 struct FieldGeom {
     unsigned waves, chunks, tiles, ranges;  // S; ceil(N / 128); tiles of 64 W targets; J ranges of the chunks
 };
-inline unsigned field_waves(unsigned n) {  // S, as plan_hermite
-    unsigned s = 1;
-    while (s < 8 && 2 * s * kFieldChunk <= n) s *= 2;
-    return s;
-}
+inline unsigned  field_waves(unsigned n) { return stream_waves(n); }
 inline FieldGeom field_geometry(unsigned n, unsigned m, unsigned per_tile) {
-    FieldGeom g;
-    g.waves             = field_waves(n);
-    g.chunks            = (n + kFieldChunk - 1) / kFieldChunk;
-    g.tiles             = (m + per_tile - 1) / per_tile;
-    const unsigned need = (kFieldTarget + g.tiles - 1) / g.tiles, most = g.chunks / g.waves;
-    unsigned       cap  = 1;  // the largest power of two <= chunks / S: every wave of every range has a chunk
-    while (2 * cap <= most) cap *= 2;
-    g.ranges = 1;
-    while (g.ranges < need && g.ranges < cap) g.ranges *= 2;
-    return g;
+    const StreamGeom g = stream_geometry(n, m, per_tile, kFieldTarget);
+    return FieldGeom{field_waves(n), stream_chunks(n), g.tiles, g.ranges};
 }
 
 // planes of a call that asks for the jerk / that does not: ax ay az (jx jy jz) sum of m / s

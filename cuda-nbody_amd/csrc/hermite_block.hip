@@ -11,13 +11,16 @@
 //   hermite_block_finish one lane per active slot: J partials in index order, corrector, dt_A, new level, the body's stored state
 // A step that would pass t_stop leaves go = 0 in the control record and the four launches after it return at once.
 //
-// hermite_block_eval<T, S> has hermite_eval's streaming loops (the text of hermite_stream.inc: bodies j by scalar loads U at a time into two
-// register sets, unit / mixed forms, two-level sums, SIMD-mate priority; 25 / 26 v_pk_* + 2 v_rsq_f32 per packed pair, no LDS, barrier
-// or scratch inside them) around another distribution of work: a workgroup owns one tile of 64 W ACTIVE bodies, gathered through the
-// active list from the predicted state, and one of J contiguous ranges of the chunks of bodies j.  Its S waves split the range's
-// chunks (chunk c of the range -> wave c mod S), fold through LDS in wave order, and wave 0 stores six partial sums per body, in units
-// of the reference mass, to the planes [J][6][tiles 64 W].  (tile, range) come from n_act, which the workgroup reads from the control
-// record: the launch grid is sized for the worst n_act of this N and the workgroups beyond tiles J leave.
+// hermite_block_eval<T, S> has hermite_eval's streaming loops (one text, hermite_stream.inc with wave_groups.inc, wave_mates.inc and
+// wave_fold.inc inside it: bodies j by scalar loads U at a time into two register sets, unit / mixed forms, two-level sums, SIMD-mate
+// priority, the fold; 25 / 26 v_pk_* + 2 v_rsq_f32 per packed pair, no LDS, barrier or scratch inside the loops) around another
+// distribution of work: a workgroup owns one tile of 64 W ACTIVE bodies, gathered through the active list from the predicted state, and
+// one of J contiguous ranges of the chunks of bodies j.  Its S waves split the range's chunks (chunk c of the range -> wave c mod S), fold
+// through LDS in wave order, and wave 0 stores six partial sums per body, in units of the reference mass, to the planes
+// [J][6][tiles 64 W].  (tile, range) come from n_act, which the workgroup reads from the control record: the launch grid is sized for the
+// worst n_act of this N and the workgroups beyond tiles J leave.  The kernel below is the active list, the tile / range derivation
+// (stream_geometry, wave_stream.h), the include, and the plane store.  hermite_block_finish adds the planes (range_sum.inc) and corrects
+// (hermite_correct.inc); the predictor of block_predict_count and block_sync is hermite_body.h's.
 #include "hermite_block_kernels.h"
 
 namespace nb {
@@ -26,7 +29,8 @@ namespace {
 #include "nbody_lane.h"
 
 #include "hermite_stream.h"
-static_assert(kChunk == static_cast<int>(kBlockChunk), "the geometry counts hermite_stream.h's chunks");
+
+#include "hermite_body.h"
 
 __device__ __forceinline__ unsigned long long ticks_of(int level, int max_level) {
     const int k = level < 0 ? 0 : (level > max_level ? max_level : level);
@@ -42,21 +46,21 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     using vec        = typename LT::vec;
     using raw4       = typename LT::raw4;
     using bits       = typename LT::bits;
-    constexpr int W  = LT::W;  // bodies i per lane
-    constexpr int U  = unroll_for<T>();
-    constexpr int CH = kChunk;
-    constexpr int LPT = CH / 64;
-    static_assert(CH % U == 0, "the streaming loop is unrolled by U");
+    constexpr int W      = LT::W;  // bodies i per lane
+    constexpr int U      = unroll_for<T>();
+    constexpr int STRIDE = 2;  // vec4 per body of state8
     typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx8 / x16
 
     if (ctrl->go == 0) return;
     const unsigned  n_act = ctrl->n_act;
-    const BlockGeom geom  = block_geometry(n, n_act, 64 * W);
+    const BlockGeom geom  = stream_geometry(n, n_act, 64 * W, kBlockTarget);
     if (blockIdx.x >= geom.tiles * geom.ranges) return;
-    const unsigned tile  = blockIdx.x / geom.ranges;
-    const unsigned range = blockIdx.x % geom.ranges;
-    const unsigned slots = geom.tiles * (64 * W);
+    const unsigned ranges = geom.ranges;
+    const unsigned tile   = blockIdx.x / ranges;
+    const unsigned range  = blockIdx.x % ranges;
+    const unsigned slots  = geom.tiles * (64 * W);
 
+    const T* const   pos_base = state8;
     const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state8));
     const int        tid  = threadIdx.x;
     const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -74,116 +78,12 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
         LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
     }
-    const T    m_first   = jp[0].w;  // (a scalar load)
-    const T    m_ref     = usable_unit(m_first) ? m_first : T(1);
-    const T    inv_mref  = T(1) / m_ref;
-    const bits unit_bits = __builtin_bit_cast(bits, m_ref);
-    vec        eps2      = LT::splat(eps2_in);
+    vec eps2 = LT::splat(eps2_in);
     LT::keep_in_vgpr(eps2);
-    const vec                 minus3 = LT::splat(T(-3));
-    const typename LT::Consts consts = LT::make_consts();
 
-    vec first[6], second[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) first[q] = second[q] = LT::splat(0);
-
-    // the range's chunks: [c_lo, c_hi), never empty (J <= n_chunks / S)
-    const unsigned n_chunks = block_chunks(n);
-    const unsigned c_lo     = static_cast<unsigned>(static_cast<unsigned long long>(range) * n_chunks / geom.ranges);
-    const unsigned c_hi     = static_cast<unsigned>(static_cast<unsigned long long>(range + 1) * n_chunks / geom.ranges);
-
-    auto chunk_is_unit = [&](unsigned c) -> bool {
-        const unsigned first_j = c * CH;
-        bool           same    = n - first_j >= static_cast<unsigned>(CH) || (n - first_j) % U == 0;
-#pragma unroll
-        for (int r = 0; r < LPT; ++r) {
-            const unsigned j = first_j + r * 64 + lane;
-            same             = same && (j >= n || __builtin_bit_cast(bits, state8[8 * static_cast<size_t>(j < n ? j : first_j) + 3]) == unit_bits);
-        }
-        return __builtin_amdgcn_ballot_w64(!same) == 0;
-    };
-    auto group = [&](size_t j0, BodyJ<T> (&b)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) b[u].p = jp[2 * (j0 + u)], b[u].v = jp[2 * (j0 + u) + 1];  // adjacent: one s_load_dwordx8 / x16
-    };
+    auto body_j = [&](size_t j, BodyJ<T>& b) { b.p = jp[2 * j], b.v = jp[2 * j + 1]; };  // adjacent: one s_load_dwordx8 / x16
 #include "hermite_stream.inc"
 
-    // SIMD-mate priority, as hermite_eval (plain LDS words, one writer each; no result bit depends on it)
-    __shared__ unsigned progress[4 * 8];
-    if (tid < 32) progress[tid] = 0xffffffffu;
-    __syncthreads();
-    const unsigned           simd = static_cast<unsigned>(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4));  // HW_REG_HW_ID[5:4] = SIMD_ID
-    volatile unsigned* const mine = progress + simd * 8;
-    unsigned                 done = 0;
-    if (lane == 0) mine[wave] = 0;
-
-    unsigned c       = c_lo + wave;  // wave w streams chunks c_lo + w, c_lo + w + S, ...
-    bool     unit    = c < c_hi ? chunk_is_unit(c) : false;
-    bool     is_unit = true;
-    unsigned held    = 0;
-    BodyJ<T> b0[U], b1[U];
-    if (c < c_hi && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
-    for (; c < c_hi; c += S) {
-        const bool next_unit = (c + S) < c_hi ? chunk_is_unit(c + S) : false;
-        if constexpr (S > 1) {
-            unsigned least = done;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) least = min(least, mine[q]);
-            if (static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(least))) >= done) {
-                __builtin_amdgcn_s_setprio(3);
-            } else {
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
-        const unsigned first_j = c * CH;
-        const unsigned count   = min(static_cast<unsigned>(CH), n - first_j);
-        const unsigned groups  = count / U;
-        const size_t   next    = ((c + S) < c_hi && n - (first_j + S * CH) >= static_cast<unsigned>(U)) ? static_cast<size_t>(first_j) + S * CH : first_j;
-        if (unit != is_unit || held == kFlushEvery) {
-            flush();
-            is_unit = unit, pending_scale = unit ? T(1) : inv_mref, held = 0;
-        }
-        if (groups > 0) {
-            if (unit) {
-                stream.template operator()<true>(first_j, groups, next, b0, b1);
-            } else {
-                stream.template operator()<false>(first_j, groups, next, b0, b1);
-            }
-        }
-#pragma unroll 1
-        for (unsigned jj = groups * U; jj < count; ++jj) {  // ragged end of the last chunk (mixed)
-            BodyJ<T> one[1];
-            one[0].p = jp[2 * (static_cast<size_t>(first_j) + jj)], one[0].v = jp[2 * (static_cast<size_t>(first_j) + jj) + 1];
-            compute.template operator()<false, 1>(one, first);
-        }
-        ++held;
-        unit = next_unit;
-        ++done;
-        if (lane == 0) mine[wave] = done;
-    }
-    if (lane == 0) mine[wave] = 0xffffffffu;
-    __builtin_amdgcn_s_setprio(0);
-    flush();
-
-    // fold the S partial sums (waves 1..S-1 -> wave 0) through LDS, fixed order
-    __shared__ T red[(S > 1 ? S - 1 : 1) * 6 * W * 64];
-    if (wave > 0) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) red[(((wave - 1) * 6 + q) * W + k) * 64 + lane] = LT::get(second[q], k);
-        }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll 1
-    for (int g = 1; g < S; ++g) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) LT::set(second[q], k, LT::get(second[q], k) + red[(((g - 1) * 6 + q) * W + k) * 64 + lane]);
-        }
-    }
     // planes [J][6][slots]: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
@@ -229,20 +129,6 @@ __global__ __launch_bounds__(256) void block_min_partial(const unsigned long lon
     }
     m = block_fold(m, lds_next, lds_level);
     if (threadIdx.x == 0) min_part[blockIdx.x] = m.next, lvl_part[blockIdx.x] = m.level;
-}
-
-// the predictor of nb_hermite_step_* (hermite_predict) for one body
-template <typename T> __device__ __forceinline__ void predict_body(const typename Lane<T>::vec4& x, const typename Lane<T>::vec4& v, const typename Lane<T>::vec4& a,
-                                                                 const typename Lane<T>::vec4& j, T dt, typename Lane<T>::vec4& xp, typename Lane<T>::vec4& vp) {
-    const T h = dt * T(0.5), t = dt * (T(1) / T(3));
-    xp.x = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.x, a.x), v.x), x.x);
-    xp.y = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.y, a.y), v.y), x.y);
-    xp.z = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.z, a.z), v.z), x.z);
-    xp.w = x.w;
-    vp.x = __builtin_fma(dt, __builtin_fma(h, j.x, a.x), v.x);
-    vp.y = __builtin_fma(dt, __builtin_fma(h, j.y, a.y), v.y);
-    vp.z = __builtin_fma(dt, __builtin_fma(h, j.z, a.z), v.z);
-    vp.w = 0;
 }
 
 template <typename T> __global__ __launch_bounds__(256) void block_predict_count(BlockArgs<T> a, unsigned partials) {
@@ -366,32 +252,15 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_block_finis
     const unsigned n_act = a.ctrl->n_act;
     const unsigned slot  = blockIdx.x * 256u + threadIdx.x;
     if (slot >= n_act) return;
-    const BlockGeom          geom  = block_geometry(a.n, n_act, per_tile);
+    const BlockGeom          geom  = stream_geometry(a.n, n_act, per_tile, kBlockTarget);
     const size_t             slots = static_cast<size_t>(geom.tiles) * per_tile;
     const unsigned long long now   = a.ctrl->now;
     const size_t             i     = a.active[slot];
-    T                        sum[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) sum[q] = a.partial[q * slots + slot];
-    // the other ranges in index order, eight ranges' loads in flight at a time (one lane's J x 6 dependent round trips to L2 were a third
-    // of a block step with a handful of active bodies)
-#pragma unroll 1
-    for (unsigned r0 = 1; r0 < geom.ranges; r0 += 8) {
-        T part[8][6];
-#pragma unroll
-        for (unsigned u = 0; u < 8; ++u) {
-            const size_t r = r0 + u < geom.ranges ? r0 + u : r0;
-#pragma unroll
-            for (int q = 0; q < 6; ++q) part[u][q] = a.partial[(r * 6 + q) * slots + slot];
-        }
-#pragma unroll
-        for (unsigned u = 0; u < 8; ++u) {
-            if (r0 + u < geom.ranges) {
-#pragma unroll
-                for (int q = 0; q < 6; ++q) sum[q] += part[u][q];
-            }
-        }
-    }
+    // sum[6]: the J ranges' partial sums of this slot, in range order
+    constexpr int            NS      = 6;
+    const T* const           partial = a.partial;
+    const unsigned           ranges  = geom.ranges;
+#include "range_sum.inc"
     const T m_first = a.state8[3];
     const T m_ref   = usable_unit(m_first) ? m_first : T(1);
     vec4    a1, j1;
@@ -404,21 +273,12 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_block_finis
     const unsigned long long own   = 1ull << (a.p.max_level - k);
     const double             dt_i  = static_cast<double>(own) * q;
     const T                  dt    = static_cast<T>(dt_i);
-    // the corrector of nb_hermite_step_*
-    const T    h = dt * T(0.5), d12 = dt * dt * (T(1) / T(12));
+    // the corrector of nb_hermite_step_*, with the body's own dt
     const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
     vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
     const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
     const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
-    vec4       x1;
-    const T    v1x = __builtin_fma(d12, j0.x - j1.x, __builtin_fma(h, a0.x + a1.x, v.x));
-    const T    v1y = __builtin_fma(d12, j0.y - j1.y, __builtin_fma(h, a0.y + a1.y, v.y));
-    const T    v1z = __builtin_fma(d12, j0.z - j1.z, __builtin_fma(h, a0.z + a1.z, v.z));
-    x1.x = __builtin_fma(d12, a0.x - a1.x, __builtin_fma(h, v.x + v1x, x.x));
-    x1.y = __builtin_fma(d12, a0.y - a1.y, __builtin_fma(h, v.y + v1y, x.y));
-    x1.z = __builtin_fma(d12, a0.z - a1.z, __builtin_fma(h, v.z + v1z, x.z));
-    x1.w = x.w;
-    v.x = v1x, v.y = v1y, v.z = v1z;
+#include "hermite_correct.inc"
     reinterpret_cast<vec4*>(a.pos)[i]  = x1;
     reinterpret_cast<vec4*>(a.vel)[i]  = v;
     reinterpret_cast<vec4*>(a.acc)[i]  = a1;

@@ -5,13 +5,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include "wave_stream.h"
+
 namespace nb {
 
 // Body indices are `unsigned`, element offsets 64-bit.  The fixed-order scan of the per-block active counts is ONE workgroup of 1 024
 // lanes, each folding N / 2^18 counts serially: 64 at 2^24 bodies, where the library stops.
 inline constexpr unsigned kBlockMaxBodies  = 1u << 24;
 inline constexpr int      kBlockMaxLevel   = 40;
-inline constexpr unsigned kBlockChunk      = 128;   // bodies j per wave and chunk (hermite_eval's)
 #ifndef NB_BLOCK_TARGET
 #define NB_BLOCK_TARGET 512  // (tools/hermite_block_bench.py measures builds with other values: make EXP=-DNB_BLOCK_TARGET=...)
 #endif
@@ -38,29 +39,13 @@ struct BlockCtrl {  // what one block step passes from launch to launch (workspa
 };
 
 // ---- geometry: a function of (N, n_act, precision) alone --------------------------------------------------------------------------
-struct BlockGeom {
-    unsigned tiles, ranges;  // tiles of 64 W active bodies; J ranges of chunks of bodies j
-};
-__host__ __device__ inline unsigned block_waves(unsigned n) {  // S, as plan_hermite
-    unsigned s = 1;
-    while (s < 8 && 2 * s * kBlockChunk <= n) s *= 2;
-    return s;
-}
-__host__ __device__ inline unsigned block_chunks(unsigned n) { return (n + kBlockChunk - 1) / kBlockChunk; }
-__host__ __device__ inline unsigned block_range_cap(unsigned n) {  // the largest power of two <= n_chunks / S: every wave of every range has a chunk
-    const unsigned most = block_chunks(n) / block_waves(n);
-    unsigned       cap  = 1;
-    while (2 * cap <= most) cap *= 2;
-    return cap;
-}
-__host__ __device__ inline BlockGeom block_geometry(unsigned n, unsigned n_act, unsigned per_tile) {
-    BlockGeom g;
-    g.tiles             = (n_act + per_tile - 1) / per_tile;
-    const unsigned need = (kBlockTarget + g.tiles - 1) / (g.tiles ? g.tiles : 1), cap = block_range_cap(n);
-    g.ranges            = 1;
-    while (g.ranges < need && g.ranges < cap) g.ranges *= 2;
-    return g;
-}
+using BlockGeom = StreamGeom;  // tiles of 64 W active bodies; J ranges of chunks of bodies j
+__host__ __device__ inline unsigned block_waves(unsigned n) { return stream_waves(n); }
+__host__ __device__ inline unsigned block_chunks(unsigned n) { return stream_chunks(n); }
+__host__ __device__ inline unsigned block_range_cap(unsigned n) { return stream_range_cap(n); }
+// stream_geometry with this library's target, for the host; hermite_block_eval and hermite_block_finish call stream_geometry by its own
+// name (wave_stream.h says why)
+inline BlockGeom block_geometry(unsigned n, unsigned n_act, unsigned per_tile) { return stream_geometry(n, n_act, per_tile, kBlockTarget); }
 // the launch grid: an upper bound of tiles * J over every n_act <= N (J > 1 means tiles * J / 2 < target)
 __host__ __device__ inline unsigned block_launch_groups(unsigned n, unsigned per_tile) {
     const unsigned           tiles_max = (n + per_tile - 1) / per_tile;

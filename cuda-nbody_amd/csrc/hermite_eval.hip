@@ -17,6 +17,11 @@
 // then added to the lane's second-level sum, scaled once (1, or 1 / m_ref).  Two levels of <= 1 024 and <= N / (1 024 S) + form
 // changes terms keep an fp32 sum at a few 1e-6 of its term magnitudes for any N.  The order depends on (N, precision) and the
 // masses alone, so results are bit-identical from call to call, stream to stream and device to device.
+//
+// Where the text lives.  The kernel below is its arguments, its bodies i, how one body j is addressed, and its epilogue; everything
+// between the bodies i and the sums -- the interaction, the chunk loop, SIMD-mate priority, the fold -- is hermite_stream.inc (with
+// wave_groups.inc, wave_mates.inc and wave_fold.inc inside it), which hermite_block_eval includes too.  The predictor is
+// hermite_body.h, the corrector hermite_correct.inc, S and the chunk count wave_stream.h.
 #include "hermite_kernels.h"
 
 namespace nb {
@@ -25,6 +30,8 @@ namespace {
 #include "nbody_lane.h"
 
 #include "hermite_stream.h"
+
+#include "hermite_body.h"
 
 template <typename T, int S, bool STEP>
 __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_eval(HermiteArgs<T> a) {
@@ -35,10 +42,7 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     using bits          = typename LT::bits;
     constexpr int W     = LT::W;  // bodies i per lane
     constexpr int U     = unroll_for<T>();
-    constexpr int CH    = kChunk;
-    constexpr int LPT   = CH / 64;
     constexpr int STRIDE = STEP ? 2 : 1;  // vec4 per body where the bodies are read
-    static_assert(CH % U == 0, "the streaming loop is unrolled by U");
     typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx4/x8/x16
 
     const T* const   pos_base = STEP ? a.state8 : a.pos;
@@ -62,132 +66,18 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
         LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
     }
-    const T    m_first  = jp[0].w;  // (a scalar load)
-    const T    m_ref    = usable_unit(m_first) ? m_first : T(1);
-    const T    inv_mref = T(1) / m_ref;
-    const bits unit_bits = __builtin_bit_cast(bits, m_ref);
-    vec        eps2     = LT::splat(a.eps2);
+    vec eps2 = LT::splat(a.eps2);
     LT::keep_in_vgpr(eps2);
-    const vec minus3 = LT::splat(T(-3));
-    const typename LT::Consts consts = LT::make_consts();
 
-    // sums: ax ay az jx jy jz.  `first`: the register sum of the current form; `second`: the lane's second-level sum, in units of m_ref
-    vec first[6], second[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) first[q] = second[q] = LT::splat(0);
-
-    const unsigned n_chunks = (n + CH - 1) / CH;
-
-    // Is every mass of chunk c the reference mass?  Each lane looks at LPT masses with an ordinary vector load, one chunk ahead.
-    // (A chunk that is not a whole number of groups -- the last -- takes the mixed loop, and its odd bodies go one by one.)
-    auto chunk_is_unit = [&](unsigned c) -> bool {
-        const unsigned first_j = c * CH;
-        bool           same    = n - first_j >= static_cast<unsigned>(CH) || (n - first_j) % U == 0;
-#pragma unroll
-        for (int r = 0; r < LPT; ++r) {
-            const unsigned j = first_j + r * 64 + lane;
-            same             = same && (j >= n || __builtin_bit_cast(bits, pos_base[(4 * STRIDE) * static_cast<size_t>(j < n ? j : first_j) + 3]) == unit_bits);
-        }
-        return __builtin_amdgcn_ballot_w64(!same) == 0;
-    };
-    auto group = [&](size_t j0, BodyJ<T> (&b)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if constexpr (STEP) {
-                b[u].p = jp[2 * (j0 + u)], b[u].v = jp[2 * (j0 + u) + 1];  // adjacent: one s_load_dwordx8 / x16
-            } else {
-                b[u].p = jp[j0 + u], b[u].v = jv[j0 + u];
-            }
+    constexpr unsigned range = 0, ranges = 1;  // every workgroup streams every chunk
+    auto body_j = [&](size_t j, BodyJ<T>& b) {
+        if constexpr (STEP) {
+            b.p = jp[2 * j], b.v = jp[2 * j + 1];  // adjacent: one s_load_dwordx8 / x16
+        } else {
+            b.p = jp[j], b.v = jv[j];
         }
     };
-
 #include "hermite_stream.inc"
-
-    // The SIMD arbiter is oldest-first: left alone, the waves that share a SIMD finish equal shares of work one after the other and
-    // the last runs alone at a lower issue rate (nbody_fast_stream.inc has the measurements).  As there, each wave publishes how many
-    // chunks it has done; one that is level with the slowest wave of ITS SIMD runs at priority 3, one that is ahead at 0.  The
-    // chunk -> wave assignment stays static, so no result bit depends on it.  (Plain LDS words, one writer each; a stale read only
-    // delays a priority change.)
-    __shared__ unsigned progress[4 * 8];  // [SIMD][wave of the workgroup]: chunks done; 0xffffffff: not on this SIMD, or finished
-    if (tid < 32) progress[tid] = 0xffffffffu;
-    __syncthreads();
-    const unsigned           simd = static_cast<unsigned>(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4));  // HW_REG_HW_ID[5:4] = SIMD_ID
-    volatile unsigned* const mine = progress + simd * 8;
-    unsigned                 done = 0;
-    if (lane == 0) mine[wave] = 0;
-
-    unsigned c       = wave;  // wave w streams chunks w, w+S, w+2S, ...
-    bool     unit    = c < n_chunks ? chunk_is_unit(c) : false;
-    bool     is_unit = true;  // the form `first` holds
-    unsigned held    = 0;     // chunks in `first`
-    BodyJ<T> b0[U], b1[U];
-    if (c < n_chunks && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
-    for (; c < n_chunks; c += S) {
-        const bool next_unit = (c + S) < n_chunks ? chunk_is_unit(c + S) : false;  // (its loads are in flight across the compute below)
-        if constexpr (S > 1) {
-            unsigned least = done;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) least = min(least, mine[q]);
-            if (static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(least))) >= done) {
-                __builtin_amdgcn_s_setprio(3);
-            } else {
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
-        const unsigned first_j = c * CH;
-        const unsigned count   = min(static_cast<unsigned>(CH), n - first_j);
-        const unsigned groups  = count / U;
-        // the wave's next chunk, when it has a whole group (else anything readable: the set is not used again)
-        const size_t next = ((c + S) < n_chunks && n - (first_j + S * CH) >= static_cast<unsigned>(U)) ? static_cast<size_t>(first_j) + S * CH : first_j;
-        if (unit != is_unit || held == kFlushEvery) {
-            flush();
-            is_unit = unit, pending_scale = unit ? T(1) : inv_mref, held = 0;
-        }
-        if (groups > 0) {
-            if (unit) {
-                stream.template operator()<true>(first_j, groups, next, b0, b1);
-            } else {
-                stream.template operator()<false>(first_j, groups, next, b0, b1);
-            }
-        }
-#pragma unroll 1
-        for (unsigned jj = groups * U; jj < count; ++jj) {  // ragged end of the range (a mixed chunk)
-            BodyJ<T> one[1];
-            if constexpr (STEP) {
-                one[0].p = jp[2 * (static_cast<size_t>(first_j) + jj)], one[0].v = jp[2 * (static_cast<size_t>(first_j) + jj) + 1];
-            } else {
-                one[0].p = jp[static_cast<size_t>(first_j) + jj], one[0].v = jv[static_cast<size_t>(first_j) + jj];
-            }
-            compute.template operator()<false, 1>(one, first);
-        }
-        ++held;
-        unit = next_unit;
-        ++done;
-        if (lane == 0) mine[wave] = done;
-    }
-    if (lane == 0) mine[wave] = 0xffffffffu;  // finished: never the one the others defer to
-    __builtin_amdgcn_s_setprio(0);
-    flush();
-
-    // fold the S partial sums (waves 1..S-1 -> wave 0) through LDS, fixed order
-    __shared__ T red[(S > 1 ? S - 1 : 1) * 6 * W * 64];
-    if (wave > 0) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) red[(((wave - 1) * 6 + q) * W + k) * 64 + lane] = LT::get(second[q], k);
-        }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll 1
-    for (int g = 1; g < S; ++g) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) LT::set(second[q], k, LT::get(second[q], k) + red[(((g - 1) * 6 + q) * W + k) * 64 + lane]);
-        }
-    }
 
 #pragma unroll
     for (int k = 0; k < W; ++k) {
@@ -198,21 +88,12 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         a1.x = LT::get(second[0], k) * m_ref, a1.y = LT::get(second[1], k) * m_ref, a1.z = LT::get(second[2], k) * m_ref, a1.w = 0;
         j1.x = LT::get(second[3], k) * m_ref, j1.y = LT::get(second[4], k) * m_ref, j1.z = LT::get(second[5], k) * m_ref, j1.w = 0;
         if constexpr (STEP) {
-            // the corrector:  v1 = v + (a0 + a1) dt/2 + (j0 - j1) dt^2/12,   x1 = x + (v + v1) dt/2 + (a0 - a1) dt^2/12
-            const T    h = a.dt * T(0.5), d12 = a.dt * a.dt * (T(1) / T(12));
+            const T    dt = a.dt;
             const vec4 x  = reinterpret_cast<const vec4*>(a.old_pos)[i];
             vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
             const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
             const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
-            vec4       x1;
-            const T    v1x = __builtin_fma(d12, j0.x - j1.x, __builtin_fma(h, a0.x + a1.x, v.x));
-            const T    v1y = __builtin_fma(d12, j0.y - j1.y, __builtin_fma(h, a0.y + a1.y, v.y));
-            const T    v1z = __builtin_fma(d12, j0.z - j1.z, __builtin_fma(h, a0.z + a1.z, v.z));
-            x1.x = __builtin_fma(d12, a0.x - a1.x, __builtin_fma(h, v.x + v1x, x.x));
-            x1.y = __builtin_fma(d12, a0.y - a1.y, __builtin_fma(h, v.y + v1y, x.y));
-            x1.z = __builtin_fma(d12, a0.z - a1.z, __builtin_fma(h, v.z + v1z, x.z));
-            x1.w = x.w;
-            v.x = v1x, v.y = v1y, v.z = v1z;
+#include "hermite_correct.inc"
             reinterpret_cast<vec4*>(a.new_pos)[i] = x1;
             reinterpret_cast<vec4*>(a.vel)[i]     = v;
         }
@@ -221,23 +102,15 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     }
 }
 
-// The predictor: x_p = x + v dt + a dt^2/2 + j dt^3/6, v_p = v + a dt + j dt^2/2 -> state8 {x_p, m, v_p, 0}.  HBM-bound.
+// The predictor (hermite_body.h) -> state8 {x_p, m, v_p, 0}.  HBM-bound.
 template <typename T> __global__ __launch_bounds__(256) void hermite_predict(const T* pos, const T* vel, const T* acc, const T* jerk, T* state8, unsigned n, T dt) {
     using vec4       = typename Lane<T>::vec4;
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const vec4 x = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i];
     const vec4 a = reinterpret_cast<const vec4*>(acc)[i], j = reinterpret_cast<const vec4*>(jerk)[i];
-    const T    h = dt * T(0.5), t = dt * (T(1) / T(3));
     vec4       xp, vp;
-    xp.x = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.x, a.x), v.x), x.x);
-    xp.y = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.y, a.y), v.y), x.y);
-    xp.z = __builtin_fma(dt, __builtin_fma(h, __builtin_fma(t, j.z, a.z), v.z), x.z);
-    xp.w = x.w;
-    vp.x = __builtin_fma(dt, __builtin_fma(h, j.x, a.x), v.x);
-    vp.y = __builtin_fma(dt, __builtin_fma(h, j.y, a.y), v.y);
-    vp.z = __builtin_fma(dt, __builtin_fma(h, j.z, a.z), v.z);
-    vp.w = 0;
+    predict_body<T>(x, v, a, j, dt, xp, vp);
     reinterpret_cast<vec4*>(state8)[2 * static_cast<size_t>(i)]     = xp;
     reinterpret_cast<vec4*>(state8)[2 * static_cast<size_t>(i) + 1] = vp;
 }
@@ -328,14 +201,13 @@ template <typename T, bool STEP> hipError_t launch_planned(const HermiteArgs<T>&
 }  // namespace
 
 // Geometry, a function of (N, precision) alone.  One vector of bodies i per lane (I = W: 12 state vectors, 6 second-level sums and two
-// chains of 9 temporaries compile to 103 - 118 VGPRs; a second vector does not fit under 128), so a workgroup owns 64 W bodies i.  S, the waves that split j, is
-// the largest power of two up to 8 that still gives every wave a whole chunk of 128 bodies j: from 65 536 bodies (fp32; 32 768
-// fp64) the grid alone puts 16 waves on every CU of the MI355X.
+// chains of 9 temporaries compile to 103 - 118 VGPRs; a second vector does not fit under 128), so a workgroup owns 64 W bodies i.  S, the waves that split j
+// (stream_waves, wave_stream.h), is the largest power of two up to 8 that still gives every wave a whole chunk of 128 bodies j: from
+// 65 536 bodies (fp32; 32 768 fp64) the grid alone puts 16 waves on every CU of the MI355X.
 template <typename T> HermitePlan plan_hermite(unsigned n) {
     constexpr int W = Lane<T>::W;
-    int           S = 1;
-    while (S < 8 && static_cast<unsigned>(2 * S) * kChunk <= n) S *= 2;
-    HermitePlan p;
+    const int     S = static_cast<int>(stream_waves(n));
+    HermitePlan   p;
     p.bodies_per_lane = W;
     p.waves           = S;
     p.unroll          = unroll_for<T>();

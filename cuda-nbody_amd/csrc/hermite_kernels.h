@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "wave_stream.h"
+
 namespace nb {
 
 // Index arithmetic: body indices are `unsigned`, element offsets 64-bit; a launch holds N / (64 W) workgroups of at most 512

@@ -1,11 +1,8 @@
-// hermite_stream.h -- what the two acceleration + jerk kernels (hermite_eval.hip, hermite_block.hip) share at namespace scope: the
-// chunking constants, s^-2 and s^-3 from s^2, a body j as the scalar unit loads it.  Included inside each translation unit's own anonymous
-// namespace, after nbody_lane.h (device code, internal linkage).  The kernel-body text they share is hermite_stream.inc.
+// hermite_stream.h -- what the acceleration + jerk kernels (hermite_eval.hip, hermite_block.hip) and field.hip share at namespace scope
+// beside wave_stream.h (the chunk, the unroll, the geometry: every *_kernels.h of the three includes it): s^-2 and s^-3 from s^2, a body j
+// as the scalar unit loads it.  Included inside each translation unit's own anonymous namespace, after nbody_lane.h (device code, internal
+// linkage).  The kernel-body text the two Hermite kernels share is hermite_stream.inc.
 #pragma once
-
-constexpr int kChunk      = 128;  // bodies j per wave and chunk
-constexpr int kFlushEvery = 8;    // chunks a register sum may collect
-template <typename T> constexpr int unroll_for() { return sizeof(T) == 8 ? 2 : 4; }  // U: a body j is 8 (fp32) / 16 (fp64) scalar registers
 
 // s^-2 and s^-3 from s2.  fp32: v_rsq_f32 (1 ulp) and two products.  fp64: the v_rsq_f64 seed y0 (relative error <= 2^-23) and, with
 // r = 1 - s2 y0^2 (|r| <= 2^-22), the series of Lane<double>::coupling for y0^3 (1-r)^(-3/2) and y0^2 (1 + r + r^2) for y0^2 / (1-r).

@@ -1,9 +1,57 @@
-// hermite_stream.inc -- the interaction and the streaming loops of the acceleration + jerk kernels, as TEXT included inside the kernel body
-// (hermite_eval in hermite_eval.hip, hermite_block_eval in hermite_block.hip; no include guard).  The kernel defines before it: T, LT, vec, U;
-// the lane's bodies i px, py, pz, vx, vy, vz; eps2, minus3, consts; the sums first[6], second[6]; and group(j0, b): the scalar loads of U
-// bodies j.  It gets: compute, whole, arrived, stream (a chunk's groups, one load group ahead), pending_scale and flush.
-    // UB bodies j against the lane's vector of bodies i, written stage by stage: UB independent chains in flight
-    auto compute = [&]<bool UNIT, int UB>(const BodyJ<T>* b, vec (&sum)[6]) {
+// hermite_stream.inc -- everything the acceleration + jerk kernels share between loading their bodies i and storing their sums, as TEXT
+// included inside the kernel body (hermite_eval in hermite_eval.hip, hermite_block_eval in hermite_block.hip; no include guard): the
+// interaction, the streaming loops (wave_groups.inc), the chunk loop of a wave with its unit / mixed forms and two-level sums, SIMD-mate
+// priority (wave_mates.inc) and the fold of the S waves (wave_fold.inc).
+//
+// The kernel defines before it: T, LT, vec, bits, W, U, S; n, tid, wave, lane; the lane's bodies i px, py, pz, vx, vy, vz; eps2; and
+//   range, ranges       the workgroup streams range `range` of the J = `ranges` contiguous ranges of the chunks of bodies j
+//   jp                  the scalar-load pointer whose element 0 is body 0's {x, y, z, m}
+//   pos_base, STRIDE    body j's {x, y, z, m} is the vec4 at pos_base + 4 STRIDE j (an ordinary pointer: the masses, one chunk ahead)
+//   body_j(j, b)        the scalar loads of body j into b
+// It gets: m_ref and, in wave 0 alone (the other waves return inside), second[6]: ax ay az jx jy jz of the lane's bodies i over the
+// workgroup's chunks, in units of m_ref.
+    constexpr int NS  = 6;
+    constexpr int CH  = kChunk;
+    constexpr int LPT = CH / 64;
+    static_assert(CH % U == 0, "the streaming loop is unrolled by U");
+
+    const T    m_first   = jp[0].w;  // (a scalar load)
+    const T    m_ref     = usable_unit(m_first) ? m_first : T(1);
+    const T    inv_mref  = T(1) / m_ref;
+    const bits unit_bits = __builtin_bit_cast(bits, m_ref);
+    const vec  minus3    = LT::splat(T(-3));
+    const typename LT::Consts consts = LT::make_consts();
+
+    // sums: ax ay az jx jy jz.  `first`: the register sum of the current form; `second`: the lane's second-level sum, in units of m_ref
+    vec first[NS], second[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) first[q] = second[q] = LT::splat(0);
+
+    // the range's chunks: [c_lo, c_hi), never empty (J <= n_chunks / S)
+    const unsigned n_chunks = stream_chunks(n);
+    const unsigned c_lo     = static_cast<unsigned>(static_cast<unsigned long long>(range) * n_chunks / ranges);
+    const unsigned c_hi     = static_cast<unsigned>(static_cast<unsigned long long>(range + 1) * n_chunks / ranges);
+
+    // Is every mass of chunk c the reference mass?  Each lane looks at LPT masses with an ordinary vector load, one chunk ahead.
+    // (A chunk that is not a whole number of groups -- the last -- takes the mixed loop, and its odd bodies go one by one.)
+    auto chunk_is_unit = [&](unsigned c) -> bool {
+        const unsigned first_j = c * CH;
+        bool           same    = n - first_j >= static_cast<unsigned>(CH) || (n - first_j) % U == 0;
+#pragma unroll
+        for (int r = 0; r < LPT; ++r) {
+            const unsigned j = first_j + r * 64 + lane;
+            same             = same && (j >= n || __builtin_bit_cast(bits, pos_base[(4 * STRIDE) * static_cast<size_t>(j < n ? j : first_j) + 3]) == unit_bits);
+        }
+        return __builtin_amdgcn_ballot_w64(!same) == 0;
+    };
+    auto group = [&](size_t j0, BodyJ<T> (&b)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) body_j(j0 + u, b[u]);
+    };
+
+    // UB bodies j against the lane's vector of bodies i, written stage by stage: UB independent chains in flight.  (wave_groups.inc passes
+    // the index of the first; nothing here depends on it.)
+    auto compute = [&]<bool UNIT, int UB>(const BodyJ<T>* b, unsigned, vec (&sum)[NS]) {
         vec dx[UB], dy[UB], dz[UB], ex[UB], ey[UB], ez[UB], s2[UB], rv[UB], k3[UB];
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
@@ -31,33 +79,56 @@
             sum[3] = LT::fma(ex[u], k3[u], sum[3]), sum[4] = LT::fma(ey[u], k3[u], sum[4]), sum[5] = LT::fma(ez[u], k3[u], sum[5]);
         }
     };
-    // a group of U bodies j in stage blocks of UB: fp32 2 x 2 (four chains' temporaries at once took the kernel to 127 VGPRs, and the
-    // S = 1 instantiation into scratch; two blocks of two compile to 93 - 95), fp64 one block of 2
-    constexpr int UB = sizeof(T) == 8 ? U : U / 2;
-    auto whole = [&]<bool UNIT>(const BodyJ<T> (&b)[U]) {
-#pragma unroll
-        for (int h = 0; h < U; h += UB) compute.template operator()<UNIT, UB>(b + h, first);
-    };
-    auto arrived = [](const BodyJ<T> (&b)[U]) { asm volatile("" : : "s"(b[0].p) : "memory"); };  // what follows is issued after the set's wait
-    // b0 holds (or is loading) group 0 of the chunk at body `chunk`; on return it is loading the first group at body `next`
-    auto stream = [&]<bool UNIT>(size_t chunk, unsigned groups, size_t next, BodyJ<T> (&b0)[U], BodyJ<T> (&b1)[U]) {
-        unsigned g = 0;
-#pragma unroll 1
-        for (; g + 2 <= groups; g += 2) {
-            arrived(b0);
-            group(chunk + (g + 1) * U, b1);
-            __builtin_amdgcn_sched_barrier(0);  // (the load stays ahead of the compute it overlaps)
-            whole.template operator()<UNIT>(b0);
-            arrived(b1);
-            group(g + 2 < groups ? chunk + (g + 2) * U : next, b0);
-            __builtin_amdgcn_sched_barrier(0);
-            whole.template operator()<UNIT>(b1);
-        }
-        if (g < groups) whole.template operator()<UNIT>(b0);  // (odd count: the ragged last chunk, nothing follows it)
-    };
+#include "wave_groups.inc"
     T    pending_scale = T(1);  // what `first` is still to be multiplied by
     auto flush         = [&]() {
         const vec scale = LT::splat(pending_scale);
 #pragma unroll
-        for (int q = 0; q < 6; ++q) second[q] = LT::fma(first[q], scale, second[q]), first[q] = LT::splat(0);
+        for (int q = 0; q < NS; ++q) second[q] = LT::fma(first[q], scale, second[q]), first[q] = LT::splat(0);
     };
+
+#define WAVE_MATES_SETUP
+#include "wave_mates.inc"
+
+    unsigned c       = c_lo + wave;  // wave w streams chunks c_lo + w, c_lo + w + S, ...
+    bool     unit    = c < c_hi ? chunk_is_unit(c) : false;
+    bool     is_unit = true;  // the form `first` holds
+    unsigned held    = 0;     // chunks in `first`
+    BodyJ<T> b0[U], b1[U];
+    if (c < c_hi && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
+    for (; c < c_hi; c += S) {
+        const bool next_unit = (c + S) < c_hi ? chunk_is_unit(c + S) : false;  // (its loads are in flight across the compute below)
+#define WAVE_MATES_CHUNK
+#include "wave_mates.inc"
+        const unsigned first_j = c * CH;
+        const unsigned count   = min(static_cast<unsigned>(CH), n - first_j);
+        const unsigned groups  = count / U;
+        // the wave's next chunk, when it has a whole group (else anything readable: the set is not used again)
+        const size_t next = ((c + S) < c_hi && n - (first_j + S * CH) >= static_cast<unsigned>(U)) ? static_cast<size_t>(first_j) + S * CH : first_j;
+        if (unit != is_unit || held == kFlushEvery) {
+            flush();
+            is_unit = unit, pending_scale = unit ? T(1) : inv_mref, held = 0;
+        }
+        if (groups > 0) {
+            if (unit) {
+                stream.template operator()<true>(first_j, groups, next, b0, b1);
+            } else {
+                stream.template operator()<false>(first_j, groups, next, b0, b1);
+            }
+        }
+#pragma unroll 1
+        for (unsigned jj = groups * U; jj < count; ++jj) {  // ragged end of the last chunk (mixed)
+            BodyJ<T> one[1];
+            body_j(static_cast<size_t>(first_j) + jj, one[0]);
+            compute.template operator()<false, 1>(one, first_j + jj, first);
+        }
+        ++held;
+        unit = next_unit;
+#define WAVE_MATES_DONE
+#include "wave_mates.inc"
+    }
+#define WAVE_MATES_LEAVE
+#include "wave_mates.inc"
+    flush();
+
+#include "wave_fold.inc"
