@@ -36,6 +36,8 @@ HERMITE_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_LIB", os.path.j
 NEIGHBOUR_LIB_PATH = os.environ.get("NBODY_HIP_NEIGHBOUR_LIB", os.path.join(HERE, "libnbody_hip_neighbour.so"))
 # Acceleration, jerk and potential of N sources at M points of the caller's own (include/nbody_hip_field.h) are a seventh, loaded by field_lib().
 FIELD_LIB_PATH = os.environ.get("NBODY_HIP_FIELD_LIB", os.path.join(HERE, "libnbody_hip_field.so"))
+# The K nearest neighbours, local densities and the density centre (include/nbody_hip_knn.h) are an eighth, loaded by knn_lib().
+KNN_LIB_PATH = os.environ.get("NBODY_HIP_KNN_LIB", os.path.join(HERE, "libnbody_hip_knn.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -346,8 +348,37 @@ FIELD_SIGNATURES = {
     "nb_field_eval_f64": (_ci, [_vp, _vp, _cu, _vp, _vp, _vp, _cu, _cd, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# include/nbody_hip_knn.h: exported by libnbody_hip_knn.so, and nothing else is
+class KnnStructure(ctypes.Structure):
+    """nb_knn_structure_t: 128 bytes of device memory a survey with the record writes"""
+    _fields_ = [("sum_density", _cd), ("centre", _cd * 3), ("density_radius", _cd), ("core_radius", _cd), ("max_density", _cd), ("min_kth_dist_sq", _cd),
+                ("max_kth_dist_sq", _cd), ("max_density_body", ctypes.c_uint32), ("defined", ctypes.c_uint32), ("degenerate", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 10)]
+
+
+class KnnPlan(ctypes.Structure):
+    """nb_knn_plan_t: the geometry of a survey, a function of N, K and the precision"""
+    _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("unroll", _ci), ("capacity", _ci), ("ranges", _cu), ("tiles", _cu), ("block_threads", _cu),
+                ("lds_bytes", _cu), ("chunks", _cu), ("blocks", _cu), ("search_launches", _cu), ("structure_launches", _cu),
+                ("density_offset", ctypes.c_ulonglong), ("density_bytes", ctypes.c_ulonglong)]
+
+
+KNN_MAX_K = 16
+KNN_SPHERE = 4.188790204786391
+KNN_DEGENERATE = 1
+KNN_NO_DENSITY = 2
+KNN_SIGNATURES = {
+    "nb_knn_workspace_bytes": (_ci, [_cu, _cu, _cu, _P(_sz)]),
+    "nb_knn_plan_f32": (_ci, [_cu, _cu, _P(KnnPlan)]),
+    "nb_knn_plan_f64": (_ci, [_cu, _cu, _P(KnnPlan)]),
+    # positions N K | knn_index knn_dist_sq densities structure | workspace workspace_bytes stream
+    "nb_knn_survey_f32": (_ci, [_vp, _cu, _cu, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nb_knn_survey_f64": (_ci, [_vp, _cu, _cu, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 _neighbour_lib = None
+_knn_lib = None
 _field_lib = None
 _ensemble_lib = None
 _hermite_lib = None
@@ -457,6 +488,21 @@ def field_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _field_lib = handle
     return _field_lib
+
+
+def knn_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_knn.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _knn_lib
+    if _knn_lib is None:
+        if not os.path.exists(KNN_LIB_PATH):
+            raise FileNotFoundError(f"{KNN_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(KNN_LIB_PATH)
+        for name, (restype, argtypes) in KNN_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _knn_lib = handle
+    return _knn_lib
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -1108,6 +1154,139 @@ class NeighbourSurvey:
     def free(self) -> None:
         for b in self._buffers():
             b.free()
+
+
+def knn_plan(num_bodies: int, k: int, dtype=np.float32) -> KnnPlan:
+    """nb_knn_plan_*: the geometry of a survey of the `k` nearest neighbours of `num_bodies` bodies"""
+    p = KnnPlan()
+    fn = knn_lib().nb_knn_plan_f32 if np.dtype(dtype) == np.float32 else knn_lib().nb_knn_plan_f64
+    check(fn(num_bodies, k, ctypes.byref(p)), "nb_knn_plan")
+    return p
+
+
+def knn_workspace_bytes(num_bodies: int, k: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(knn_lib().nb_knn_workspace_bytes(num_bodies, k, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_knn_workspace_bytes")
+    return out.value
+
+
+def knn_structure_dict(record: KnnStructure) -> dict:
+    out = {name: getattr(record, name) for name, _ in KnnStructure._fields_ if name not in ("reserved", "centre")}
+    out["centre"] = tuple(record.centre)
+    return out
+
+
+class KnnSurvey:
+    """The K nearest neighbours of every body, local densities and the structure record of states of N bodies (include/nbody_hip_knn.h).
+
+    The outputs, the record, the workspace and a staging copy of the positions are device buffers owned here, sized for `max_k`.
+    ``positions`` is a device address (a DeviceBuffer, its ``ptr`` or an int: T[4 N], only read) or a host array of shape (N, 4)
+    {x, y, z, m}.  ``survey`` enqueues on `stream`, waits for it and returns numpy arrays plus the record as a dict; ``enqueue_survey``
+    only enqueues (outputs stay on the device: see the ``*_ptr`` attributes)."""
+
+    def __init__(self, num_bodies: int, dtype=np.float32, max_k: int = KNN_MAX_K):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies = n = int(num_bodies)
+        self.max_k = int(max_k)
+        self._workspace_bytes = knn_workspace_bytes(n, self.max_k, self.dtype)  # refuses the sizes the calls refuse; the same for every K
+        size = self.dtype.itemsize
+        self._pos = DeviceBuffer(4 * n * size)
+        self._index, self._dist_sq = DeviceBuffer(4 * n * self.max_k), DeviceBuffer(size * n * self.max_k)
+        self._densities = DeviceBuffer(n * size)
+        self._structure = DeviceBuffer(ctypes.sizeof(KnnStructure))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+        self._positions = None  # what the last survey looked at: a host copy, or the device address
+        self._centre = None  # the density centre of the last survey with the record
+
+    def _buffers(self):
+        return [self._pos, self._index, self._dist_sq, self._densities, self._structure, self._workspace]
+
+    def enqueue_survey(self, positions, k: int, densities=None, structure=None, stream=None) -> None:
+        """`densities` and `structure` default to k >= 2 (the calls refuse them with k = 1)"""
+        k = int(k)
+        if not 1 <= k <= self.max_k:
+            raise ValueError(f"k must be in 1 .. {self.max_k}")
+        densities = k >= 2 if densities is None else bool(densities)
+        structure = k >= 2 if structure is None else bool(structure)
+        if isinstance(positions, DeviceBuffer):
+            address = self._positions = positions.ptr
+        elif isinstance(positions, (int, ctypes.c_void_p)):
+            address = self._positions = positions
+        else:
+            host = np.ascontiguousarray(positions, dtype=self.dtype)
+            if host.shape != (self.num_bodies, 4):
+                raise ValueError(f"expected an array of shape {(self.num_bodies, 4)}, got {host.shape}")
+            self._pos.upload(host)
+            address, self._positions = self._pos.ptr, host.copy()
+        fn = getattr(knn_lib(), "nb_knn_survey_" + self._suffix)
+        check(fn(address, self.num_bodies, k, self._index.ptr, self._dist_sq.ptr, self._densities.ptr if densities else None,
+                 self._structure.ptr if structure else None, self._workspace.ptr, self._workspace_bytes, stream), "nb_knn_survey")
+
+    def structure(self, stream=None) -> dict:
+        out = KnnStructure()
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+        check(lib().nb_d2h(ctypes.byref(out), self._structure.ptr, ctypes.sizeof(out), stream), "nb_d2h(structure)")
+        return knn_structure_dict(out)
+
+    def survey(self, positions, k: int, densities=None, structure=None, stream=None) -> dict:
+        self.enqueue_survey(positions, k, densities, structure, stream)
+        n, k = self.num_bodies, int(k)
+        densities = k >= 2 if densities is None else bool(densities)
+        structure = k >= 2 if structure is None else bool(structure)
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+        out = {"knn_index": self._index.download(np.empty((n, k), dtype=np.uint32)), "knn_dist_sq": self._dist_sq.download(np.empty((n, k), dtype=self.dtype))}
+        out["densities"] = self._densities.download(np.empty(n, dtype=self.dtype)) if densities else None
+        out["structure"] = self.structure(stream) if structure else None
+        self._centre = out["structure"]["centre"] if structure else None
+        return out
+
+    def lagrangian_radii(self, fractions, centre=None) -> np.ndarray:
+        """For each fraction f the distance from the density centre of the last ``survey`` (or from `centre`) at which the cumulative mass,
+        bodies taken by distance, first reaches f M.  Host work: the positions are downloaded, distances are float64, one sort."""
+        centre = self._centre if centre is None else centre
+        if centre is None or self._positions is None:
+            raise RuntimeError("lagrangian_radii needs a survey with the structure record (or a centre) first")
+        if isinstance(self._positions, np.ndarray):
+            pos = self._positions
+        else:
+            pos = np.empty((self.num_bodies, 4), dtype=self.dtype)
+            address = self._positions if isinstance(self._positions, (int, ctypes.c_void_p)) else self._positions.value
+            check(lib().nb_d2h(pos.ctypes.data_as(_vp), address, pos.nbytes, None), "nb_d2h(positions)")
+        return lagrangian_radii(pos, centre, fractions)
+
+    @property
+    def knn_index_ptr(self):
+        return self._index.ptr
+
+    @property
+    def knn_dist_sq_ptr(self):
+        return self._dist_sq.ptr
+
+    @property
+    def densities_ptr(self):
+        return self._densities.ptr
+
+    @property
+    def structure_ptr(self):
+        return self._structure.ptr
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+def lagrangian_radii(positions, centre, fractions) -> np.ndarray:
+    """positions (N, 4) {x, y, z, m}: for each fraction f the smallest distance from `centre` whose bodies (all within it, in float64) hold
+    at least f times the total mass"""
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 4)
+    r = np.sqrt(((pos[:, :3] - np.asarray(centre, dtype=np.float64)) ** 2).sum(axis=1))
+    order = np.argsort(r, kind="stable")
+    cumulative = np.cumsum(pos[order, 3])
+    at = np.searchsorted(cumulative, np.asarray(fractions, dtype=np.float64) * cumulative[-1], side="left")
+    return r[order][np.minimum(at, len(r) - 1)]
 
 
 def field_plan(num_sources: int, num_targets: int, dtype=np.float32) -> FieldPlan:

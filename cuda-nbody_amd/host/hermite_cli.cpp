@@ -5,6 +5,7 @@
 #include "bodysystemhip_hermite_block.hpp"
 #include "compute.hpp"
 #include "field_cli.hpp"
+#include "knn_cli.hpp"
 #include "neighbour_cli.hpp"
 #include "randomise_bodies.hpp"
 #include "text.hpp"
@@ -103,6 +104,12 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
         system.get_positions(pos);
         report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
     };
+    const auto report_structure = [&]() {  // (of the synchronised snapshot)
+        if (run.knn == 0) return;
+        system.sync();
+        system.get_positions(pos);
+        report_knn(std::span<const T>(pos), run.knn);
+    };
     const auto report_field_points = [&]() {  // (of the synchronised snapshot)
         if (run.field_points.empty()) return;
         system.sync();
@@ -138,6 +145,7 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
     report("", none, end);
     report_energy(run.steps);
     report_neighbourhood();
+    report_structure();
     report_field_points();
 }
 
@@ -165,6 +173,11 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         if (run.neighbours < 0) return;
         system.get_positions(pos);
         report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
+    };
+    const auto report_structure = [&]() {
+        if (run.knn == 0) return;
+        system.get_positions(pos);
+        report_knn(std::span<const T>(pos), run.knn);
     };
     const auto report_field_points = [&]() {
         if (run.field_points.empty()) return;
@@ -202,6 +215,7 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
     }
     report_energy(run.steps);
     report_neighbourhood();
+    report_structure();
     report_field_points();
 }
 

@@ -18,6 +18,7 @@ struct HermiteRun {
     std::size_t           steps = 0;
     std::filesystem::path dump;
     bool                  energy = false;
+    unsigned              knn = 0;  // --knn=<K> (0: not asked for): report_knn of the final state
     double                neighbours = -1.0;  // --neighbours=<radius> (< 0: not asked for): report_neighbours of the final state
     std::vector<double>   field_points;  // --field=<file>: x y z of every point (empty: not asked for): report_field of the final state
     bool                  block = false;  // --integrator=hermite-block: dt_max = the demo row's dt, `steps` / `iterations` count intervals of dt_max

@@ -6,7 +6,7 @@
 //                     --tipsy=<file> -i,--iterations=<n> --blockSize=<n>      (single-dash spellings accepted too)
 //   extensions      : --numdevices=<n> | --devices=<list> (the NVIDIA sample's -numdevices, which this fork of it dropped)
 //                     --mode=fast|strict  --config=shell|random|expand  --demo=<0..6>  --steps=<n>  --dump=<file>
-//                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --neighbours=<radius>  --field=<file>  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
+//                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --neighbours=<radius>  --knn=<K>  --field=<file>  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
@@ -14,10 +14,12 @@
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
 #include "../../include/nbody_hip_hermite_block.h"
+#include "../../include/nbody_hip_knn.h"
 #include "../../include/nbody_hip_neighbour.h"
 #include "compute.hpp"
 #include "field_cli.hpp"
 #include "integrate_nbody_hip.hpp"
+#include "knn_cli.hpp"
 #include "neighbour_cli.hpp"
 
 #include <dlfcn.h>  // (the --alloc-limit-mib test hook lives in the lab library: looked up, never linked)
@@ -64,6 +66,7 @@ struct Options {
     bool                  no_workspace = false;
     bool                  energy = false;  // print the energy at the start and the end of a --benchmark / --steps run
     std::optional<double> neighbours;  // --neighbours=<radius>: after the run, the closest pair, the neighbour counts within the radius, the deepest potential
+    std::optional<unsigned> knn;  // --knn=<K>: after the run, the density centre, the density and core radii, the densest body, the Lagrangian radii
     std::vector<double>   field_points;  // --field=<file>: x y z of the points where the final state's acceleration and potential are printed
     std::size_t           workspace_mib = 0;  // 0: no bound of our own
     std::size_t           alloc_limit_mib = 0;  // test hook: device allocations above this are refused (0: none)
@@ -112,6 +115,10 @@ Options:
   --neighbours FLOAT          After a --benchmark, --steps or --dump run: print the closest pair of bodies and its separation, the mean and
                               the largest number of neighbours within this radius (>= 0) and its body, the deepest potential and its
                               body (one device only, at most 16777216 bodies; accepted wherever --energy is)
+  --knn UINT                  After a --benchmark, --steps or --dump run: from the K (2 to 16) nearest neighbours of every body print the
+                              density centre, the density and core radii, the densest body, the smallest and largest K-th-neighbour
+                              distance and the 10 %, 50 % and 90 % Lagrangian radii about the density centre (one device only, at
+                              most 16777216 bodies; accepted wherever --neighbours is)
   --field FILE                After a --benchmark, --steps or --dump run: print the acceleration and the potential of the final state at
                               every point of this text file (one `x y z` per line, `#` comments, 1 to 65536 points; softened as the
                               run, no body excluded; one device only; accepted wherever --energy is)
@@ -288,6 +295,12 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
                 if (!ok) return error("--neighbours: Value not a radius (a finite number >= 0)");
                 options.neighbours = radius;
             }
+        } else if (name == "knn") {
+            const auto v = take_value();
+            unsigned   k = 0;
+            ok           = v && parse_number(*v, k) && k >= 2 && k <= NB_KNN_MAX_K;
+            if (!ok) return error("--knn: Value not in range 2 to 16");
+            options.knn = k;
         } else if (name == "field") {
             const auto v = take_value();
             ok           = v.has_value();
@@ -318,6 +331,10 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
     if (options.neighbours && (options.compare || options.qatest)) return error("--neighbours cannot be combined with --compare or --qatest (those runs step two systems)");
     if (options.neighbours && options.numbodies > NB_NEIGHBOUR_MAX_BODIES) return error("--neighbours: --numbodies must be at most 16777216");
 
+    if (options.knn && options.devices.size() > 1) return error("--knn is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
+    if (options.knn && (options.compare || options.qatest)) return error("--knn cannot be combined with --compare or --qatest (those runs step two systems)");
+    if (options.knn && options.numbodies > NB_NEIGHBOUR_MAX_BODIES) return error("--knn: --numbodies must be at most 16777216");
+
     const auto field = !options.field_points.empty();
     if (field && options.devices.size() > 1) return error("--field is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
     if (field && (options.compare || options.qatest)) return error("--field cannot be combined with --compare or --qatest (those runs step two systems)");
@@ -327,8 +344,8 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         if (options.numbodies > 65536) return error("--systems: --numbodies must be at most 65536 (above that one system fills the GPU: run it without --systems)");
         if (options.numbodies * options.systems > (std::size_t{1} << 31)) return error("--systems: numbodies * systems must be at most 2^31");
         if (options.devices.size() > 1) return error("--systems is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
-        if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.energy || options.neighbours || field || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
-            return error("--systems cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --energy, --neighbours, --field, --no-workspace, --workspace-mib or --cpu");
+        if (options.hostmem || !options.tipsy.empty() || options.compare || options.qatest || options.graph || options.energy || options.neighbours || options.knn || field || options.no_workspace || options.workspace_mib != 0 || options.cpu) {
+            return error("--systems cannot be combined with --hostmem, --tipsy, --compare, --qatest, --graph, --energy, --neighbours, --knn, --field, --no-workspace, --workspace-mib or --cpu");
         }
     }
 
@@ -416,6 +433,7 @@ auto main(int argc, char** argv) -> int {
             run.dump       = cmd_options.dump;
             run.energy     = cmd_options.energy;
             run.neighbours = cmd_options.neighbours.value_or(-1.0);
+            run.knn        = cmd_options.knn.value_or(0u);
             run.field_points = cmd_options.field_points;
             run.block      = cmd_options.hermite_block;
             run.eta        = cmd_options.eta.value_or(run.eta);
@@ -456,6 +474,15 @@ auto main(int argc, char** argv) -> int {
                 report_neighbours(compute.positions_fp32(), *cmd_options.neighbours, softening * softening);
             }
         };
+        // ... and then its density centre and radii
+        const auto report_structure = [&]() {
+            if (!cmd_options.knn) return;
+            if (compute.fp64_enabled()) {
+                report_knn(compute.positions_fp64(), *cmd_options.knn);
+            } else {
+                report_knn(compute.positions_fp32(), *cmd_options.knn);
+            }
+        };
         // ... and then its field at the points of --field
         const auto report_field_points = [&]() {
             if (cmd_options.field_points.empty()) return;
@@ -471,6 +498,7 @@ auto main(int argc, char** argv) -> int {
             compute.run_benchmark(nb_iterations);
             report_energy(1 + static_cast<std::size_t>(nb_iterations));  // (run_benchmark takes one untimed step first)
             report_neighbourhood();
+            report_structure();
             report_field_points();
             return 0;
         }
@@ -489,6 +517,7 @@ auto main(int argc, char** argv) -> int {
         }
         report_energy(cmd_options.steps);
         report_neighbourhood();
+        report_structure();
         report_field_points();
         return 0;
     } catch (const std::invalid_argument& e) {
