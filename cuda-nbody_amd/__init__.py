@@ -38,6 +38,9 @@ NEIGHBOUR_LIB_PATH = os.environ.get("NBODY_HIP_NEIGHBOUR_LIB", os.path.join(HERE
 FIELD_LIB_PATH = os.environ.get("NBODY_HIP_FIELD_LIB", os.path.join(HERE, "libnbody_hip_field.so"))
 # The K nearest neighbours, local densities and the density centre (include/nbody_hip_knn.h) are an eighth, loaded by knn_lib().
 KNN_LIB_PATH = os.environ.get("NBODY_HIP_KNN_LIB", os.path.join(HERE, "libnbody_hip_knn.so"))
+# Hermite steps of many independent systems, a time step per system (include/nbody_hip_hermite_ensemble.h) are a ninth, loaded by
+# hermite_ensemble_lib().
+HERMITE_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite_ensemble.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -376,7 +379,53 @@ KNN_SIGNATURES = {
     "nb_knn_survey_f64": (_ci, [_vp, _cu, _cu, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# include/nbody_hip_hermite_ensemble.h: exported by libnbody_hip_hermite_ensemble.so, and nothing else is
+class HermiteEnsemblePlan(ctypes.Structure):
+    """nb_hermite_ensemble_plan_t: nb_hermite_plan_t per system, and the grid"""
+    _fields_ = [("bodies_per_lane", ctypes.c_int), ("waves_per_group", ctypes.c_int), ("unroll", ctypes.c_int), ("groups", ctypes.c_uint),
+                ("block_threads", ctypes.c_uint), ("lds_bytes", ctypes.c_uint), ("groups_per_system", ctypes.c_uint), ("reserved", ctypes.c_uint),
+                ("grid_blocks", ctypes.c_ulonglong)]
+
+
+class HermiteEnsembleClock(ctypes.Structure):
+    """nb_hermite_ensemble_clock_t: 32 bytes of device memory per system"""
+    _fields_ = [("time", ctypes.c_double), ("dt_next", ctypes.c_double), ("dt_last", ctypes.c_double), ("steps", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class HermiteEnsembleStatus(ctypes.Structure):
+    """nb_hermite_ensemble_status_t: 64 bytes of device memory nb_hermite_ensemble_advance_* writes"""
+    _fields_ = [("systems", ctypes.c_uint32), ("done", ctypes.c_uint32), ("stalled", ctypes.c_uint32), ("stepped", ctypes.c_uint32),
+                ("total_steps", ctypes.c_uint64), ("min_time", ctypes.c_double), ("min_dt_last", ctypes.c_double), ("reserved", ctypes.c_uint64 * 3)]
+
+
+HERMITE_ENSEMBLE_CLOCK_DTYPE = np.dtype([("time", "<f8"), ("dt_next", "<f8"), ("dt_last", "<f8"), ("steps", "<u4"), ("flags", "<u4")])
+HERMITE_ENSEMBLE_MAX_BODIES = 65536
+HERMITE_ENSEMBLE_MAX_TOTAL = 1 << 28
+HERMITE_ENSEMBLE_DONE, HERMITE_ENSEMBLE_STALLED = 1, 2
+HERMITE_ENSEMBLE_SIGNATURES = {
+    "nb_hermite_ensemble_workspace_bytes": (_ci, [_cu, _cu, _cu, _P(_sz)]),
+    "nb_hermite_ensemble_plan_f32": (_ci, [_cu, _cu, _P(HermiteEnsemblePlan)]),
+    "nb_hermite_ensemble_plan_f64": (_ci, [_cu, _cu, _P(HermiteEnsemblePlan)]),
+    # accelerations jerks positions velocities | N B | softening_sq system_softening_sq | stream
+    "nb_hermite_ensemble_eval_f32": (_ci, [_vp, _vp, _vp, _vp, _cu, _cu, _cf, _vp, _vp]),
+    "nb_hermite_ensemble_eval_f64": (_ci, [_vp, _vp, _vp, _vp, _cu, _cu, _cd, _vp, _vp]),
+    # new_positions old_positions velocities accelerations jerks | workspace workspace_bytes | N B | delta_time softening_sq system_params | stream
+    "nb_hermite_ensemble_step_f32": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cu, _cf, _cf, _vp, _vp]),
+    "nb_hermite_ensemble_step_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cu, _cd, _cd, _vp, _vp]),
+    # accelerations jerks | N B | eta dt_out | workspace workspace_bytes | stream
+    "nb_hermite_ensemble_timestep_f32": (_ci, [_vp, _vp, _cu, _cu, _cf, _vp, _vp, _sz, _vp]),
+    "nb_hermite_ensemble_timestep_f64": (_ci, [_vp, _vp, _cu, _cu, _cd, _vp, _vp, _sz, _vp]),
+    # accelerations jerks positions velocities clocks | N B | softening_sq system_softening_sq eta | workspace workspace_bytes | stream
+    "nb_hermite_ensemble_begin_f32": (_ci, [_vp, _vp, _vp, _vp, _vp, _cu, _cu, _cf, _vp, _cf, _vp, _sz, _vp]),
+    "nb_hermite_ensemble_begin_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _cu, _cu, _cd, _vp, _cd, _vp, _sz, _vp]),
+    # new_positions old_positions velocities accelerations jerks clocks status | workspace workspace_bytes | N B | t_stop dt_max eta softening_sq
+    # system_softening_sq | stream
+    "nb_hermite_ensemble_advance_f32": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cu, _cd, _cd, _cf, _cf, _vp, _vp]),
+    "nb_hermite_ensemble_advance_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cu, _cd, _cd, _cd, _cd, _vp, _vp]),
+}
+
 _lib = None
+_hermite_ensemble_lib = None
 _neighbour_lib = None
 _knn_lib = None
 _field_lib = None
@@ -443,6 +492,21 @@ def hermite_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _hermite_lib = handle
     return _hermite_lib
+
+
+def hermite_ensemble_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _hermite_ensemble_lib
+    if _hermite_ensemble_lib is None:
+        if not os.path.exists(HERMITE_ENSEMBLE_LIB_PATH):
+            raise FileNotFoundError(f"{HERMITE_ENSEMBLE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(HERMITE_ENSEMBLE_LIB_PATH)
+        for name, (restype, argtypes) in HERMITE_ENSEMBLE_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _hermite_ensemble_lib = handle
+    return _hermite_ensemble_lib
 
 
 def hermite_block_lib() -> ctypes.CDLL:
@@ -870,6 +934,143 @@ class HermiteSystem:
         out = np.empty(1, dtype=self.dtype)
         check(lib().nb_d2h(out.ctypes.data_as(_vp), self._dt.ptr, out.nbytes, stream), "nb_d2h")
         return out[0]
+
+    def _download(self, buf: DeviceBuffer) -> np.ndarray:
+        return buf.download(np.empty(self.shape, dtype=self.dtype))
+
+    def get_positions(self) -> np.ndarray:
+        return self._download(self._pos)
+
+    def get_velocities(self) -> np.ndarray:
+        return self._download(self._vel)
+
+    def get_accelerations(self) -> np.ndarray:
+        return self._download(self._acc)
+
+    def get_jerks(self) -> np.ndarray:
+        return self._download(self._jerk)
+
+    def synchronize(self) -> None:
+        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+def hermite_ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> HermiteEnsemblePlan:
+    """nb_hermite_ensemble_plan_*: the geometry of `num_systems` systems of `num_bodies` bodies"""
+    p = HermiteEnsemblePlan()
+    fn = getattr(hermite_ensemble_lib(), "nb_hermite_ensemble_plan_" + ("f32" if np.dtype(dtype) == np.float32 else "f64"))
+    check(fn(num_bodies, num_systems, ctypes.byref(p)), "nb_hermite_ensemble_plan")
+    return p
+
+
+def hermite_ensemble_workspace_bytes(num_bodies: int, num_systems: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(hermite_ensemble_lib().nb_hermite_ensemble_workspace_bytes(num_bodies, num_systems, np.dtype(dtype).itemsize, ctypes.byref(out)),
+          "nb_hermite_ensemble_workspace_bytes")
+    return out.value
+
+
+class HermiteEnsemble:
+    """B independent systems of N bodies on the device, stepped together by the 4th-order Hermite scheme of
+    include/nbody_hip_hermite_ensemble.h.
+
+    Positions (stepped in place: the calls allow new == old), velocities, accelerations and jerks of 4*N*B T, the workspace, the clocks and
+    the status record are owned here; arrays go in and out as (B, N, 4).  ``set_state`` uploads positions {x, y, z, m} and velocities;
+    ``eval`` fills the stored accelerations and jerks (what starts a fixed-dt run); ``step(dt)`` takes one step of every system, dt a
+    scalar or one value per system; ``suggested_dt(eta)`` reads eta * min |a| / |jerk| of every system back.  The adaptive form:
+    ``begin(eta)``, then ``advance(t_stop, eta, dt_max, calls)`` enqueues `calls` calls without reading anything back; ``clocks()`` and
+    ``status()`` read the device records.  `softening_sq`: a scalar or one value per system."""
+
+    def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, softening_sq=None):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies, self.num_systems = int(num_bodies), int(num_systems)
+        t = self.dtype.type
+        self._workspace_bytes = hermite_ensemble_workspace_bytes(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
+        self.shape = (self.num_systems, self.num_bodies, 4)
+        nbytes = 4 * self.num_bodies * self.num_systems * self.dtype.itemsize
+        self._pos, self._vel, self._acc, self._jerk = (DeviceBuffer(nbytes) for _ in range(4))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._clocks = DeviceBuffer(ctypes.sizeof(HermiteEnsembleClock) * self.num_systems)
+        self._status = DeviceBuffer(ctypes.sizeof(HermiteEnsembleStatus))
+        self._per_system = DeviceBuffer(self.num_systems * self.dtype.itemsize)  # dt_out
+        self._params = DeviceBuffer(4 * self.num_systems * self.dtype.itemsize)
+        self._system_eps2 = None
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+        softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else softening_sq
+        if np.ndim(softening_sq) == 0:
+            self.softening_sq = np.full(self.num_systems, softening_sq, self.dtype)
+        else:
+            self.softening_sq = np.ascontiguousarray(softening_sq, dtype=self.dtype)
+            if self.softening_sq.shape != (self.num_systems,):
+                self.free()
+                raise ValueError(f"softening_sq: a scalar or {self.num_systems} values")
+            self._system_eps2 = DeviceBuffer(self.softening_sq.nbytes)
+            self._system_eps2.upload(self.softening_sq)
+
+    def _buffers(self):
+        return [b for b in (self._pos, self._vel, self._acc, self._jerk, self._workspace, self._clocks, self._status, self._per_system, self._params, self._system_eps2)
+                if b is not None]
+
+    def _fn(self, name):
+        return getattr(hermite_ensemble_lib(), f"nb_hermite_ensemble_{name}_{self._suffix}")
+
+    def _softening(self):
+        return self._scalar(self.softening_sq[0]), (self._system_eps2.ptr if self._system_eps2 is not None else None)
+
+    def set_state(self, positions, velocities) -> None:
+        for buf, data in ((self._pos, positions), (self._vel, velocities)):
+            data = np.ascontiguousarray(data, dtype=self.dtype)
+            if data.shape != self.shape:
+                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
+            buf.upload(data)
+
+    def eval(self, stream=None) -> None:
+        check(self._fn("eval")(self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self.num_systems, *self._softening(), stream),
+              "nb_hermite_ensemble_eval")
+
+    def step(self, delta_time, stream=None) -> None:
+        """One step of every system: `delta_time` a scalar, or one dt per system (uploaded first, with the systems' softening^2)."""
+        table = None
+        if np.ndim(delta_time) != 0 or self._system_eps2 is not None:
+            table = np.zeros((self.num_systems, 4), self.dtype)
+            table[:, 0], table[:, 1] = delta_time, self.softening_sq
+            self._params.upload(table)
+        check(self._fn("step")(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
+                               self.num_systems, self._scalar(0 if table is not None else delta_time), self._scalar(self.softening_sq[0]),
+                               self._params.ptr if table is not None else None, stream), "nb_hermite_ensemble_step")
+
+    def suggested_dt(self, eta, stream=None) -> np.ndarray:
+        check(self._fn("timestep")(self._acc.ptr, self._jerk.ptr, self.num_bodies, self.num_systems, self._scalar(eta), self._per_system.ptr, self._workspace.ptr,
+                                   self._workspace_bytes, stream), "nb_hermite_ensemble_timestep")
+        out = np.empty(self.num_systems, dtype=self.dtype)
+        check(lib().nb_d2h(out.ctypes.data_as(_vp), self._per_system.ptr, out.nbytes, stream), "nb_d2h")
+        return out
+
+    def begin(self, eta, stream=None) -> None:
+        check(self._fn("begin")(self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self._clocks.ptr, self.num_bodies, self.num_systems, *self._softening(),
+                                self._scalar(eta), self._workspace.ptr, self._workspace_bytes, stream), "nb_hermite_ensemble_begin")
+
+    def advance(self, t_stop, eta, dt_max=float("inf"), calls: int = 1, stream=None) -> None:
+        """`calls` calls of nb_hermite_ensemble_advance_*: every system that can still move takes `calls` steps towards t_stop; nothing is read back."""
+        for _ in range(calls):
+            check(self._fn("advance")(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._clocks.ptr, self._status.ptr, self._workspace.ptr,
+                                      self._workspace_bytes, self.num_bodies, self.num_systems, float(t_stop), float(dt_max), self._scalar(eta), *self._softening(), stream),
+                  "nb_hermite_ensemble_advance")
+
+    def clocks(self) -> np.ndarray:
+        """the systems' clocks as a structured array (HERMITE_ENSEMBLE_CLOCK_DTYPE)"""
+        return self._clocks.download(np.empty(self.num_systems, dtype=HERMITE_ENSEMBLE_CLOCK_DTYPE))
+
+    def status(self) -> HermiteEnsembleStatus:
+        """the status record of the last advance"""
+        raw = self._status.download(np.empty(ctypes.sizeof(HermiteEnsembleStatus), dtype=np.uint8))
+        return HermiteEnsembleStatus.from_buffer_copy(raw.tobytes())
 
     def _download(self, buf: DeviceBuffer) -> np.ndarray:
         return buf.download(np.empty(self.shape, dtype=self.dtype))

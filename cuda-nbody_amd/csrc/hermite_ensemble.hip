@@ -1,0 +1,374 @@
+// hermite_ensemble.hip -- the kernels of libnbody_hip_hermite_ensemble.so (include/nbody_hip_hermite_ensemble.h): 4th-order Hermite steps
+// of B independent systems of N bodies in one launch per stage, each system with a time step of its own.  gfx950 only; FMA contraction on.
+//
+// hermite_ensemble_eval<T, S, STEP> is hermite_eval (hermite_eval.hip) per system: workgroup g works on tile g mod G of system g / G, G the
+// workgroups plan_hermite gives one system of N bodies, S = stream_waves(N).  What lies between a lane's bodies i and its sums is the
+// same TEXT (hermite_stream.inc with wave_groups.inc, wave_mates.inc and wave_fold.inc inside it; hermite_body.h; hermite_correct.inc), so
+// a system's sums are formed in the order the solo kernel forms them and its bits are the solo call's.  Only the bases of the arrays, dt
+// and softening^2 are the system's own, all wave-uniform: a workgroup never touches two systems.
+//
+// The adaptive form keeps a 32-byte clock per system on the device.  Every stage of nb_hermite_ensemble_advance_* derives the system's dt
+// from that record (clock_decision), which only the clock stage -- after every stage that reads it -- writes; the workgroups of a system
+// that is done or stalled leave after that one scalar load.  No atomics anywhere: the status record is integer sums and exact minima.
+#include "hermite_ensemble_kernels.h"
+
+namespace nb {
+namespace {
+
+#include "nbody_lane.h"
+
+#include "hermite_stream.h"
+
+#include "hermite_body.h"
+
+#include "hermite_ratio.h"
+
+// softening^2 == 0: the floor of nbody_hip_hermite.h (the i = j term contributes 0, not NaN)
+template <typename T> __device__ __forceinline__ T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
+
+// The rule of nb_hermite_ensemble_advance_*, as far as it is a function of the clock before the call: does the system step, with which dt,
+// and is that step its last?
+enum : int { kSkip = 0, kFinish = 1, kStep = 2, kLastStep = 3 };
+template <typename T> __device__ __forceinline__ int clock_decision(const EnsembleClock& c, double t_stop, double dt_max, T& dt) {
+    if (c.flags & (kClockDone | kClockStalled)) return kSkip;
+    const double remaining = t_stop - c.time;
+    if (!(remaining > 0) || static_cast<T>(remaining) == T(0)) return kFinish;
+    const double cand = dt_max < c.dt_next ? dt_max : c.dt_next;
+    if (cand >= remaining) {
+        dt = static_cast<T>(remaining);
+        return kLastStep;
+    }
+    dt = static_cast<T>(cand);
+    return kStep;
+}
+
+// (read-only for the whole launch -> scalar loads where the index is wave-uniform)
+template <typename V> __device__ __forceinline__ V uniform_load(const V* p, size_t index) {
+    typedef const V __attribute__((address_space(4)))* uniform_ptr;
+    return reinterpret_cast<uniform_ptr>(reinterpret_cast<unsigned long long>(p))[index];
+}
+
+// dt and softening^2 of system s; false: the system takes no step in this call
+template <typename T, bool STEP> __device__ __forceinline__ bool system_parameters(const EnsembleSource<T>& src, unsigned s, T& dt, T& eps2) {
+    dt = src.dt, eps2 = src.eps2;
+    if (src.params != nullptr) {
+        dt   = uniform_load(src.params, 4 * static_cast<size_t>(s));
+        eps2 = uniform_load(src.params, 4 * static_cast<size_t>(s) + 1);
+    } else if (src.system_eps2 != nullptr) {
+        eps2 = uniform_load(src.system_eps2, s);
+    }
+    eps2 = floored(eps2);
+    if constexpr (STEP) {
+        if (src.clocks != nullptr) {
+            const double* const        words = reinterpret_cast<const double*>(src.clocks) + 4 * static_cast<size_t>(s);
+            const std::uint32_t* const halves = reinterpret_cast<const std::uint32_t*>(words);
+            EnsembleClock              c;
+            c.time = uniform_load(words, 0), c.dt_next = uniform_load(words, 1), c.dt_last = 0, c.steps = 0, c.flags = uniform_load(halves, 7);
+            return clock_decision<T>(c, src.t_stop, src.dt_max, dt) >= kStep;
+        }
+    }
+    return true;
+}
+
+template <typename T, int S, bool STEP>
+__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_ensemble_eval(EnsembleHermiteArgs<T> a) {
+    using LT            = Lane<T>;
+    using vec4          = typename LT::vec4;
+    using vec           = typename LT::vec;
+    using raw4          = typename LT::raw4;
+    using bits          = typename LT::bits;
+    constexpr int W     = LT::W;  // bodies i per lane
+    constexpr int U     = unroll_for<T>();
+    constexpr int STRIDE = STEP ? 2 : 1;  // vec4 per body where the bodies are read
+    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx4/x8/x16
+
+    // the workgroup's system and its tile of that system's bodies i
+    const unsigned system = blockIdx.x / a.groups_per_system;
+    const unsigned tile   = blockIdx.x - system * a.groups_per_system;
+    T              dt, eps2_system;
+    if (!system_parameters<T, STEP>(a.src, system, dt, eps2_system)) return;  // (wave-uniform: the whole workgroup leaves)
+
+    const unsigned   n        = a.n;
+    const size_t     origin   = 4 * static_cast<size_t>(system) * n;  // the system's first element in an array of T[4 N B]
+    const T* const   pos_base = STEP ? a.state8 + 2 * origin : a.pos + origin;
+    const T* const   vel_base = STEP ? a.state8 + 2 * origin + 4 : a.vel_in + origin;
+    const stream_ptr jp       = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(pos_base));
+    const stream_ptr jv       = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(vel_base));
+    const int        tid      = threadIdx.x;
+    const int        wave     = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int        lane     = tid & 63;
+
+    // bodies i of this lane: block_base + k*64 + lane (coalesced across the lanes of a wave), within the system
+    const unsigned block_base = tile * (64 * W);
+    vec            px, py, pz, vx, vy, vz;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned local = block_base + k * 64 + lane;
+        const size_t   i     = local < n ? local : n - 1;
+        const vec4     p     = reinterpret_cast<const vec4*>(pos_base)[i * STRIDE];
+        const vec4     v     = reinterpret_cast<const vec4*>(vel_base)[i * STRIDE];
+        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
+        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
+    }
+    vec eps2 = LT::splat(eps2_system);
+    LT::keep_in_vgpr(eps2);
+
+    constexpr unsigned range = 0, ranges = 1;  // every workgroup streams every chunk of its system
+    auto body_j = [&](size_t j, BodyJ<T>& b) {
+        if constexpr (STEP) {
+            b.p = jp[2 * j], b.v = jp[2 * j + 1];  // adjacent: one s_load_dwordx8 / x16
+        } else {
+            b.p = jp[j], b.v = jv[j];
+        }
+    };
+#include "hermite_stream.inc"
+
+    T* const acc  = a.acc + origin;
+    T* const jerk = a.jerk + origin;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned local = block_base + k * 64 + lane;
+        if (local >= n) continue;
+        const size_t i = local;
+        vec4         a1, j1;
+        a1.x = LT::get(second[0], k) * m_ref, a1.y = LT::get(second[1], k) * m_ref, a1.z = LT::get(second[2], k) * m_ref, a1.w = 0;
+        j1.x = LT::get(second[3], k) * m_ref, j1.y = LT::get(second[4], k) * m_ref, j1.z = LT::get(second[5], k) * m_ref, j1.w = 0;
+        if constexpr (STEP) {
+            const vec4 x  = reinterpret_cast<const vec4*>(a.old_pos + origin)[i];
+            vec4       v  = reinterpret_cast<const vec4*>(a.vel + origin)[i];
+            const vec4 a0 = reinterpret_cast<const vec4*>(acc)[i];
+            const vec4 j0 = reinterpret_cast<const vec4*>(jerk)[i];
+#include "hermite_correct.inc"
+            reinterpret_cast<vec4*>(a.new_pos + origin)[i] = x1;
+            reinterpret_cast<vec4*>(a.vel + origin)[i]     = v;
+        }
+        reinterpret_cast<vec4*>(acc)[i]  = a1;
+        reinterpret_cast<vec4*>(jerk)[i] = j1;
+    }
+}
+
+// The predictor (hermite_body.h) -> state8 {x_p, m, v_p, 0}, on the grid of the evaluation: one wave per tile of 64 W bodies.  HBM-bound.
+template <typename T>
+__global__ __launch_bounds__(64) void hermite_ensemble_predict(const T* pos, const T* vel, const T* acc, const T* jerk, T* state8, unsigned n, unsigned groups_per_system,
+                                                               EnsembleSource<T> src) {
+    using vec4          = typename Lane<T>::vec4;
+    constexpr int W     = Lane<T>::W;
+    const unsigned system = blockIdx.x / groups_per_system;
+    const unsigned tile   = blockIdx.x - system * groups_per_system;
+    T              dt, eps2;
+    if (!system_parameters<T, true>(src, system, dt, eps2)) return;
+    const size_t first = static_cast<size_t>(system) * n;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned local = tile * (64 * W) + k * 64 + threadIdx.x;
+        if (local >= n) continue;
+        const size_t i = first + local;
+        const vec4   x = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i];
+        const vec4   a = reinterpret_cast<const vec4*>(acc)[i], j = reinterpret_cast<const vec4*>(jerk)[i];
+        vec4         xp, vp;
+        predict_body<T>(x, v, a, j, dt, xp, vp);
+        reinterpret_cast<vec4*>(state8)[2 * i]     = xp;
+        reinterpret_cast<vec4*>(state8)[2 * i + 1] = vp;
+    }
+}
+
+__device__ __forceinline__ double block_min(double m, double* lds) {
+    const int tid = threadIdx.x;
+    lds[tid]      = m;
+    __syncthreads();
+#pragma unroll 1
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) lds[tid] = fmin(lds[tid], lds[tid + half]);
+        __syncthreads();
+    }
+    return lds[0];
+}
+
+// min |a|^2 / |jerk|^2 over kEnsembleTimestepBodies bodies of one system -> partial[system * partials + p].  (The minimum is exact in any
+// order, so the partials of the solo call and these give one value.)  With clocks: the systems that take no step in this call are left out.
+template <typename T>
+__global__ __launch_bounds__(256) void hermite_ensemble_timestep_partial(const T* acc, const T* jerk, unsigned n, unsigned partials, EnsembleSource<T> src, bool stepping,
+                                                                         double* partial) {
+    using vec4 = typename Lane<T>::vec4;
+    __shared__ double lds[256];
+    const unsigned    system = blockIdx.x / partials;
+    const unsigned    p      = blockIdx.x - system * partials;
+    if (stepping) {
+        T dt, eps2;
+        if (!system_parameters<T, true>(src, system, dt, eps2)) return;
+    }
+    const unsigned local = p * kEnsembleTimestepBodies + threadIdx.x;
+    double         m     = __builtin_inf();
+    if (local < n) {
+        const size_t i = static_cast<size_t>(system) * n + local;
+        m              = ratio_sq<T>(reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i]);
+    }
+    m = block_min(m, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+
+// what one system, or a block of them, adds to the status record
+struct Tally {
+    unsigned long long systems, done, stalled, stepped, total_steps;
+    double             min_time, min_dt_last;
+};
+__device__ __forceinline__ Tally block_tally(Tally t, unsigned long long (*sums)[256], double (*mins)[256]) {
+    const int tid = threadIdx.x;
+    sums[0][tid] = t.systems, sums[1][tid] = t.done, sums[2][tid] = t.stalled, sums[3][tid] = t.stepped, sums[4][tid] = t.total_steps;
+    mins[0][tid] = t.min_time, mins[1][tid] = t.min_dt_last;
+    __syncthreads();
+#pragma unroll 1
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) sums[q][tid] += sums[q][tid + half];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) mins[q][tid] = fmin(mins[q][tid], mins[q][tid + half]);
+        }
+        __syncthreads();
+    }
+    return Tally{sums[0][0], sums[1][0], sums[2][0], sums[3][0], sums[4][0], mins[0][0], mins[1][0]};
+}
+__device__ __forceinline__ void store_tally(const Tally& t, EnsembleStatus* out) {
+    EnsembleStatus s{};
+    s.systems = static_cast<std::uint32_t>(t.systems), s.done = static_cast<std::uint32_t>(t.done), s.stalled = static_cast<std::uint32_t>(t.stalled);
+    s.stepped = static_cast<std::uint32_t>(t.stepped), s.total_steps = t.total_steps, s.min_time = t.min_time, s.min_dt_last = t.min_dt_last;
+    *out = s;
+}
+
+// One thread per system: the minimum of the system's partials, dt = eta (T)sqrt(min) -- the expression of hermite_timestep_final -- and
+//   dt_out != nullptr   dt_out[s] = dt                                     (nb_hermite_ensemble_timestep_*)
+//   begin               the clock of a run that starts                      (nb_hermite_ensemble_begin_*)
+//   else                the clock after this call's step, by the rule of the header (nb_hermite_ensemble_advance_*), and the block's tally
+template <typename T>
+__global__ __launch_bounds__(256) void hermite_ensemble_clock(const double* partial, unsigned partials, unsigned b, T eta, T* dt_out, EnsembleClock* clocks, bool begin,
+                                                              EnsembleSource<T> src, EnsembleStatus* block_status) {
+    __shared__ unsigned long long sums[5][256];
+    __shared__ double             mins[2][256];
+    const unsigned                s = blockIdx.x * kEnsembleClockSystems + threadIdx.x;
+    Tally                         t{0, 0, 0, 0, 0, __builtin_inf(), __builtin_inf()};
+    if (s < b) {
+        auto next_dt = [&]() {
+            double m = __builtin_inf();
+            for (unsigned p = 0; p < partials; ++p) m = fmin(m, partial[static_cast<size_t>(s) * partials + p]);
+            return eta * static_cast<T>(__builtin_sqrt(m));
+        };
+        if (dt_out != nullptr) {
+            dt_out[s] = next_dt();
+        } else if (begin) {
+            const T       dt = next_dt();
+            EnsembleClock c{0.0, static_cast<double>(dt), 0.0, 0u, dt > T(0) ? 0u : kClockStalled};
+            clocks[s] = c;
+        } else {
+            EnsembleClock c = clocks[s];
+            T             dt;
+            const int     what = clock_decision<T>(c, src.t_stop, src.dt_max, dt);
+            if (what == kFinish) {
+                c.flags |= kClockDone, c.time = src.t_stop;
+                clocks[s] = c;
+            } else if (what >= kStep) {
+                c.time    = what == kLastStep ? src.t_stop : c.time + static_cast<double>(dt);
+                c.dt_last = static_cast<double>(dt);
+                c.steps += 1;
+                c.dt_next = static_cast<double>(next_dt());
+                if (what == kLastStep) c.flags |= kClockDone;
+                if (!(c.dt_next > 0) && !(c.flags & kClockDone)) c.flags |= kClockStalled;
+                clocks[s]     = c;
+                t.stepped     = 1;
+                t.min_dt_last = c.dt_last;
+            }
+            t.systems = 1, t.done = (c.flags & kClockDone) ? 1 : 0, t.stalled = (c.flags & kClockStalled) ? 1 : 0, t.total_steps = c.steps, t.min_time = c.time;
+        }
+    }
+    if (block_status == nullptr) return;  // (uniform: a kernel argument)
+    t = block_tally(t, sums, mins);
+    if (threadIdx.x == 0) store_tally(t, block_status + blockIdx.x);
+}
+
+// the blocks' tallies -> the status record (one workgroup)
+__global__ __launch_bounds__(256) void hermite_ensemble_status(const EnsembleStatus* block_status, unsigned blocks, EnsembleStatus* status) {
+    __shared__ unsigned long long sums[5][256];
+    __shared__ double             mins[2][256];
+    Tally                         t{0, 0, 0, 0, 0, __builtin_inf(), __builtin_inf()};
+    for (unsigned i = threadIdx.x; i < blocks; i += 256u) {
+        const EnsembleStatus r = block_status[i];
+        t.systems += r.systems, t.done += r.done, t.stalled += r.stalled, t.stepped += r.stepped, t.total_steps += r.total_steps;
+        t.min_time = fmin(t.min_time, r.min_time), t.min_dt_last = fmin(t.min_dt_last, r.min_dt_last);
+    }
+    t = block_tally(t, sums, mins);
+    if (threadIdx.x == 0) store_tally(t, status);
+}
+
+template <typename T, int S, bool STEP> hipError_t launch_s(const EnsembleHermiteArgs<T>& a, unsigned long long grid, hipStream_t stream) {
+    (void)hipGetLastError();  // a launch reports ITS OWN error
+    hipLaunchKernelGGL((hermite_ensemble_eval<T, S, STEP>), dim3(static_cast<unsigned>(grid)), dim3(64 * S), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T, bool STEP> hipError_t launch_planned(EnsembleHermiteArgs<T> a, unsigned b, hipStream_t stream) {
+    const EnsembleHermitePlan p = plan_hermite_ensemble<T>(a.n, b);
+    a.groups_per_system         = p.groups;
+    switch (p.waves) {
+        case 1: return launch_s<T, 1, STEP>(a, p.grid_blocks, stream);
+        case 2: return launch_s<T, 2, STEP>(a, p.grid_blocks, stream);
+        case 4: return launch_s<T, 4, STEP>(a, p.grid_blocks, stream);
+        case 8: return launch_s<T, 8, STEP>(a, p.grid_blocks, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+// The geometry of one system is plan_hermite's (hermite_eval.hip), a function of (N, precision) alone; B only sets the grid.
+template <typename T> EnsembleHermitePlan plan_hermite_ensemble(unsigned n, unsigned b) {
+    constexpr int       W = Lane<T>::W;
+    const int           S = static_cast<int>(stream_waves(n));
+    EnsembleHermitePlan p;
+    p.bodies_per_lane = W;
+    p.waves           = S;
+    p.unroll          = unroll_for<T>();
+    p.groups          = (n + 64u * W - 1) / (64u * W);
+    p.block_threads   = 64u * S;
+    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * W * 64 * sizeof(T));
+    p.grid_blocks     = static_cast<unsigned long long>(p.groups) * b;
+    return p;
+}
+
+template <typename T> hipError_t launch_ensemble_eval(const EnsembleHermiteArgs<T>& a, unsigned b, hipStream_t stream) { return launch_planned<T, false>(a, b, stream); }
+
+template <typename T> hipError_t launch_ensemble_step(const EnsembleHermiteArgs<T>& a, unsigned b, T* state8, hipStream_t stream) {
+    const EnsembleHermitePlan p = plan_hermite_ensemble<T>(a.n, b);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((hermite_ensemble_predict<T>), dim3(static_cast<unsigned>(p.grid_blocks)), dim3(64), 0, stream, a.old_pos, static_cast<const T*>(a.vel),
+                       static_cast<const T*>(a.acc), static_cast<const T*>(a.jerk), state8, a.n, p.groups, a.src);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    return launch_planned<T, true>(a, b, stream);
+}
+
+template <typename T>
+hipError_t launch_ensemble_clocks(const T* acc, const T* jerk, unsigned n, unsigned b, T eta, T* dt_out, EnsembleClock* clocks, bool begin, const EnsembleSource<T>& src,
+                                  double* partial, EnsembleStatus* block_status, EnsembleStatus* status, hipStream_t stream) {
+    const unsigned partials = ensemble_partials(n), blocks = ensemble_status_blocks(b);
+    const bool     stepping = dt_out == nullptr && !begin;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((hermite_ensemble_timestep_partial<T>), dim3(partials * b), dim3(256), 0, stream, acc, jerk, n, partials, src, stepping, partial);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL((hermite_ensemble_clock<T>), dim3(blocks), dim3(256), 0, stream, static_cast<const double*>(partial), partials, b, eta, dt_out, clocks, begin, src,
+                       status != nullptr ? block_status : nullptr);
+    if (const auto err = hipGetLastError(); err != hipSuccess || status == nullptr) return err;
+    hipLaunchKernelGGL(hermite_ensemble_status, dim3(1), dim3(256), 0, stream, static_cast<const EnsembleStatus*>(block_status), blocks, status);
+    return hipGetLastError();
+}
+
+template EnsembleHermitePlan plan_hermite_ensemble<float>(unsigned, unsigned);
+template EnsembleHermitePlan plan_hermite_ensemble<double>(unsigned, unsigned);
+template hipError_t          launch_ensemble_eval<float>(const EnsembleHermiteArgs<float>&, unsigned, hipStream_t);
+template hipError_t          launch_ensemble_eval<double>(const EnsembleHermiteArgs<double>&, unsigned, hipStream_t);
+template hipError_t          launch_ensemble_step<float>(const EnsembleHermiteArgs<float>&, unsigned, float*, hipStream_t);
+template hipError_t          launch_ensemble_step<double>(const EnsembleHermiteArgs<double>&, unsigned, double*, hipStream_t);
+template hipError_t launch_ensemble_clocks<float>(const float*, const float*, unsigned, unsigned, float, float*, EnsembleClock*, bool, const EnsembleSource<float>&, double*,
+                                                  EnsembleStatus*, EnsembleStatus*, hipStream_t);
+template hipError_t launch_ensemble_clocks<double>(const double*, const double*, unsigned, unsigned, double, double*, EnsembleClock*, bool, const EnsembleSource<double>&,
+                                                   double*, EnsembleStatus*, EnsembleStatus*, hipStream_t);
+
+}  // namespace nb

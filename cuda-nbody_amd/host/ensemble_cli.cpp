@@ -2,16 +2,76 @@
 #include "ensemble_cli.hpp"
 
 #include "bodyensemblehip.hpp"
+#include "bodyensemblehip_hermite.hpp"
 #include "compute.hpp"
 #include "randomise_bodies.hpp"
 #include "text.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <fstream>
 #include <stdexcept>
 #include <vector>
 
 namespace {
+
+template <typename T> auto write_dump(const EnsembleRun& run, const std::vector<T>& pos, const std::vector<T>& vel) -> void {
+    auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
+    if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
+    out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
+    out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
+}
+
+// --integrator=hermite-ensemble: --steps=K takes K fixed steps of --integrator=hermite's dt; --t-end runs the adaptive form, batches of calls
+// between reads of the 64-byte status record; --benchmark times `iterations` fixed steps after one untimed, B N^2 interactions per step
+template <typename T> auto run_hermite_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+    const auto n = run.num_bodies, b = run.num_systems;
+    // BodySystemHIP's conversions: dt float -> T, softening^2 = T(s) * T(s)
+    const T dt = static_cast<T>(run.params.time_step);
+    const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
+    auto ensemble = BodyEnsembleHIPHermite<T>(n, b, softening_sq);
+    ensemble.set_state(pos, vel);
+    if (run.benchmark) {
+        ensemble.update(dt);  // (untimed, as Compute::run_benchmark)
+        HipEvent start, stop;
+        start.record();
+        for (int i = 0; i < run.iterations; ++i) ensemble.update(dt);
+        stop.record();
+        stop.synchronize();
+        const float milliseconds = HipEvent::elapsed_ms(start, stop);
+        const float frequency    = static_cast<float>(run.iterations) * (1000.0f / milliseconds);
+        const float interactions = static_cast<float>(static_cast<double>(b) * static_cast<double>(n) * static_cast<double>(n) * 1e-9) * frequency;
+        const int   flops        = 43;  // an acceleration + jerk interaction, as --integrator=hermite counts it
+        std::printf("%zu bodies x %zu systems, hermite integrator, total time for %d iterations: %s ms\n", n, b, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("= %s ms per step\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
+        std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
+        std::printf("= %s %s-precision GFLOP/s at %d flops per acceleration + jerk interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
+                    sizeof(T) == 8 ? "double" : "single", flops);
+        return;
+    }
+    if (run.t_end > 0.0) {
+        const T eta = static_cast<T>(run.eta);
+        ensemble.begin(eta);
+        constexpr int batch = 64;  // calls between two reads of the status record
+        auto status = nb_hermite_ensemble_status_t{};
+        do {
+            for (int i = 0; i < batch; ++i) ensemble.advance(run.t_end, run.t_end, eta);
+            status = ensemble.status();
+        } while (status.done + status.stalled < status.systems && status.stepped > 0);
+        auto steps = std::vector<unsigned>();
+        for (const auto& clock : ensemble.clocks()) steps.push_back(clock.steps);
+        std::sort(steps.begin(), steps.end());
+        std::printf("%zu bodies x %zu systems, hermite integrator, eta %g, to t = %g: %u systems done, %u stalled\n", n, b, run.eta, run.t_end, status.done, status.stalled);
+        std::printf("steps per system: fewest %u, median %u, most %u; %llu in all\n", steps.front(), steps[steps.size() / 2], steps.back(), static_cast<unsigned long long>(status.total_steps));
+    } else {
+        for (std::size_t s = 0; s < run.steps; ++s) ensemble.update(dt);
+    }
+    if (!run.dump.empty()) {
+        ensemble.get_positions(pos);
+        ensemble.get_velocities(vel);
+        write_dump<T>(run, pos, vel);
+    }
+}
 
 template <typename T> auto run_typed(const EnsembleRun& run) -> void {
     const auto n = run.num_bodies, b = run.num_systems;
@@ -29,6 +89,10 @@ template <typename T> auto run_typed(const EnsembleRun& run) -> void {
         for (std::size_t s = 0; s < b; ++s) {
             randomise_bodies<T>(run.config, std::span<T>(pos).subspan(4 * n * s, 4 * n), std::span<T>(vel).subspan(4 * n * s, 4 * n), scaled.cluster_scale, scaled.velocity_scale);
         }
+    }
+    if (run.hermite) {
+        run_hermite_typed<T>(run, pos, vel);
+        return;
     }
     auto ensemble = BodyEnsembleHIP<T>(n, b, run.mode);
     ensemble.set_positions(pos);
@@ -56,10 +120,7 @@ template <typename T> auto run_typed(const EnsembleRun& run) -> void {
     if (!run.dump.empty()) {
         ensemble.get_positions(pos);
         ensemble.get_velocities(vel);
-        auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
-        if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
-        out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
-        out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
+        write_dump<T>(run, pos, vel);
     }
 }
 

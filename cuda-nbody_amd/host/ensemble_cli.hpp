@@ -1,4 +1,5 @@
-// ensemble_cli.hpp -- `nbody --systems=<B>`: B independent systems of --numbodies bodies stepped in one launch (BodyEnsembleHIP).
+// ensemble_cli.hpp -- `nbody --systems=<B>`: B independent systems of --numbodies bodies stepped in one launch (BodyEnsembleHIP), or, with
+// --integrator=hermite-ensemble, by 4th-order Hermite steps with one dt for all or a time step per system (BodyEnsembleHIPHermite).
 #pragma once
 
 #include "nbody_types.hpp"
@@ -16,6 +17,9 @@ struct EnsembleRun {
     int                   iterations = 10;
     std::size_t           steps = 0;
     std::filesystem::path dump;
+    bool                  hermite = false;  // --integrator=hermite-ensemble
+    double                t_end = 0.0;      // hermite: > 0 runs the adaptive form to this time (--t-end), else --steps fixed steps of params.time_step
+    double                eta = 0.02;       // hermite, adaptive: the accuracy parameter of the systems' time steps (--eta)
 };
 
 // Starts from the current rand() state (main has applied --seed): system 0 is the single-system start-up state (the same three

@@ -10,10 +10,12 @@
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
+//                     --integrator=hermite-ensemble --systems=<B> (... of B systems, a time step per system: libnbody_hip_hermite_ensemble.so)
 #include "ensemble_cli.hpp"
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
 #include "../../include/nbody_hip_hermite_block.h"
+#include "../../include/nbody_hip_hermite_ensemble.h"
 #include "../../include/nbody_hip_knn.h"
 #include "../../include/nbody_hip_neighbour.h"
 #include "compute.hpp"
@@ -76,7 +78,9 @@ struct Options {
     std::size_t           systems = 0;  // --systems=<B>: an ensemble of B systems (0: one system, the reference's run)
     bool                  hermite = false;  // --integrator=hermite or hermite-block (euler, the reference's step, is the default)
     bool                  hermite_block = false;  // --integrator=hermite-block
-    std::optional<double> eta;     // --eta (hermite-block)
+    bool                  hermite_ensemble = false;  // --integrator=hermite-ensemble (with --systems)
+    std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble)
+    std::optional<double> t_end;   // --t-end (hermite-ensemble)
     std::optional<int>    levels;  // --levels (hermite-block)
 };
 
@@ -132,6 +136,12 @@ Options:
                               body steps by its own dt * 2^-level, --steps=K advances to K * dt, interactions are counted as n_act * N
   --eta FLOAT [0.02]          hermite-block: accuracy parameter of the bodies' time steps (the first steps use 0.01)
   --levels UINT [30]          hermite-block: the deepest level, 0 to 40 (time steps down to dt * 2^-levels)
+  --integrator=hermite-ensemble  with --systems (required; its restrictions apply, numbodies * systems at most 2^28): Hermite steps of every
+                              system in one launch per stage.  --steps=K takes K steps of --integrator=hermite's dt, --dump writes in
+                              --systems' format, --benchmark counts B*N^2 acceleration + jerk interactions per step
+  --t-end FLOAT               hermite-ensemble: run every system to this time (> 0) with a time step of its own, eta (--eta) times the
+                              smallest |a| / |jerk| of the system, and print the systems done and stalled and the fewest, median and
+                              most steps per system
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
 
@@ -271,8 +281,8 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
         } else if (name == "integrator") {
             const auto v = take_value();
-            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite-block");
-            if (ok) options.hermite = *v != "euler", options.hermite_block = *v == "hermite-block";
+            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite-block" || *v == "hermite-ensemble");
+            if (ok) options.hermite_ensemble = *v == "hermite-ensemble", options.hermite = *v != "euler" && !options.hermite_ensemble, options.hermite_block = *v == "hermite-block";
         } else if (name == "eta") {
             const auto v = take_value();
             ok           = v.has_value();
@@ -283,6 +293,17 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
                 ok              = end != nullptr && *end == '\0' && end != text.c_str() && eta > 0.0 && eta <= 1.0;
                 if (!ok) return error("--eta: Value not in range (0, 1]");
                 options.eta = eta;
+            }
+        } else if (name == "t-end") {
+            const auto v = take_value();
+            ok           = v.has_value();
+            if (ok) {
+                char*      end   = nullptr;
+                const auto text  = std::string(*v);
+                const auto t_end = std::strtod(text.c_str(), &end);
+                ok               = end != nullptr && *end == '\0' && end != text.c_str() && std::isfinite(t_end) && t_end > 0.0;
+                if (!ok) return error("--t-end: Value not a time (a finite number > 0)");
+                options.t_end = t_end;
             }
         } else if (name == "neighbours") {
             const auto v = take_value();
@@ -361,7 +382,16 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         }
     }
 
-    if ((options.eta || options.levels) && !options.hermite_block) return error("--eta and --levels belong to --integrator=hermite-block");
+    if (options.hermite_ensemble) {
+        if (options.systems == 0) return error("--integrator=hermite-ensemble needs --systems (and an explicit --numbodies of at most 65536)");
+        if (options.numbodies * options.systems > NB_HERMITE_ENSEMBLE_MAX_TOTAL) return error("--integrator=hermite-ensemble: numbodies * systems must be at most 2^28");
+        if (options.mode == NB_MODE_STRICT) return error("--integrator=hermite-ensemble has no strict mode: there is no CPU reference arithmetic to reproduce");
+        if (options.t_end && (options.benchmark || options.steps > 0)) return error("--t-end cannot be combined with --benchmark or --steps (it runs every system to that time)");
+    }
+    if (options.t_end && !options.hermite_ensemble) return error("--t-end belongs to --integrator=hermite-ensemble");
+
+    // (--eta is hermite-ensemble's too; the message is the one the block integrator's users know)
+    if ((options.levels && !options.hermite_block) || (options.eta && !options.hermite_block && !options.hermite_ensemble)) return error("--eta and --levels belong to --integrator=hermite-block");
 
     // the reference prints this hint and the full help on every successful parse (nbody.cpp:315-316)
     std::printf("Run \" nbody - benchmark[-numbodies = <numBodies>] \" to measure performance\n");
@@ -404,7 +434,7 @@ auto main(int argc, char** argv) -> int {
         }
 
         if (cmd_options.systems > 0) {
-            if (!cmd_options.benchmark && cmd_options.steps == 0 && cmd_options.dump.empty()) throw std::invalid_argument("--systems: pass --benchmark or --steps/--dump");
+            if (!cmd_options.benchmark && cmd_options.steps == 0 && cmd_options.dump.empty() && !cmd_options.t_end) throw std::invalid_argument("--systems: pass --benchmark or --steps/--dump");
             auto run        = EnsembleRun{};
             run.fp64        = cmd_options.fp64;
             run.num_bodies  = cmd_options.numbodies;
@@ -416,6 +446,9 @@ auto main(int argc, char** argv) -> int {
             run.iterations  = cmd_options.iterations == 0 ? 10 : static_cast<int>(cmd_options.iterations);
             run.steps       = cmd_options.steps;
             run.dump        = cmd_options.dump;
+            run.hermite     = cmd_options.hermite_ensemble;
+            run.t_end       = cmd_options.t_end.value_or(0.0);
+            run.eta         = cmd_options.eta.value_or(run.eta);
             run_ensemble(run);
             return 0;
         }
