@@ -41,6 +41,9 @@ KNN_LIB_PATH = os.environ.get("NBODY_HIP_KNN_LIB", os.path.join(HERE, "libnbody_
 # Hermite steps of many independent systems, a time step per system (include/nbody_hip_hermite_ensemble.h) are a ninth, loaded by
 # hermite_ensemble_lib().
 HERMITE_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite_ensemble.so"))
+# Block time steps of many independent systems, one launch per stage (include/nbody_hip_hermite_block_ensemble.h) are a tenth, loaded by
+# hermite_block_ensemble_lib().
+HERMITE_BLOCK_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite_block_ensemble.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -424,7 +427,41 @@ HERMITE_ENSEMBLE_SIGNATURES = {
     "nb_hermite_ensemble_advance_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _cu, _cu, _cd, _cd, _cd, _cd, _vp, _vp]),
 }
 
+# include/nbody_hip_hermite_block_ensemble.h: exported by libnbody_hip_hermite_block_ensemble.so, and nothing else is
+class HermiteBlockEnsemblePlan(ctypes.Structure):
+    """nb_hermite_block_ensemble_plan_t: nb_hermite_block_plan_t of (N, n_act), and what the number of systems adds"""
+    _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("unroll", _ci), ("tiles", _cu), ("ranges", _cu), ("groups", _cu),
+                ("launch_groups", _cu), ("block_threads", _cu), ("lds_bytes", _cu), ("slots", _cu), ("chunks", _cu), ("step_launches", _cu),
+                ("partial_offset", ctypes.c_ulonglong), ("partial_bytes", ctypes.c_ulonglong), ("groups_per_system", _cu), ("blocks_per_system", _cu),
+                ("eval_grid", ctypes.c_ulonglong), ("schedule_grid", ctypes.c_ulonglong), ("workspace_stride", ctypes.c_ulonglong)]
+
+
+class HermiteBlockEnsembleSummary(ctypes.Structure):
+    """nb_hermite_block_ensemble_summary_t: the B status records folded into 64 bytes of device memory"""
+    _fields_ = [("min_now_ticks", ctypes.c_uint64), ("max_now_ticks", ctypes.c_uint64), ("block_steps", ctypes.c_uint64), ("body_steps", ctypes.c_uint64),
+                ("systems", ctypes.c_uint32), ("stopped", ctypes.c_uint32), ("deepest_level", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 5)]
+
+
+HERMITE_BLOCK_ENSEMBLE_MAX_BODIES = 65536
+HERMITE_BLOCK_ENSEMBLE_MAX_TOTAL = 1 << 28
+# positions velocities accelerations jerks ticks levels status workspace, workspace_bytes, N, B
+_block_ensemble_state = [_vp] * 8 + [_sz, _cu, _cu]
+HERMITE_BLOCK_ENSEMBLE_SIGNATURES = {
+    "nb_hermite_block_ensemble_workspace_bytes": (_ci, [_cu, _cu, _cu, _P(_sz)]),
+    "nb_hermite_block_ensemble_plan_f32": (_ci, [_cu, _cu, _cu, _P(HermiteBlockEnsemblePlan)]),
+    "nb_hermite_block_ensemble_plan_f64": (_ci, [_cu, _cu, _cu, _P(HermiteBlockEnsemblePlan)]),
+    # ... softening_sq system_softening_sq params [t_stop] stream
+    "nb_hermite_block_ensemble_init_f32": (_ci, _block_ensemble_state + [_cf, _vp, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_ensemble_init_f64": (_ci, _block_ensemble_state + [_cd, _vp, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_ensemble_step_f32": (_ci, _block_ensemble_state + [_cf, _vp, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite_block_ensemble_step_f64": (_ci, _block_ensemble_state + [_cd, _vp, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite_block_ensemble_sync_f32": (_ci, [_vp] * 8 + [_cu, _cu, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_ensemble_sync_f64": (_ci, [_vp] * 8 + [_cu, _cu, _P(HermiteBlockParams), _vp]),
+    "nb_hermite_block_ensemble_summary": (_ci, [_vp, _cu, _vp, _vp]),
+}
+
 _lib = None
+_hermite_block_ensemble_lib = None
 _hermite_ensemble_lib = None
 _neighbour_lib = None
 _knn_lib = None
@@ -507,6 +544,21 @@ def hermite_ensemble_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _hermite_ensemble_lib = handle
     return _hermite_ensemble_lib
+
+
+def hermite_block_ensemble_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite_block_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _hermite_block_ensemble_lib
+    if _hermite_block_ensemble_lib is None:
+        if not os.path.exists(HERMITE_BLOCK_ENSEMBLE_LIB_PATH):
+            raise FileNotFoundError(f"{HERMITE_BLOCK_ENSEMBLE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(HERMITE_BLOCK_ENSEMBLE_LIB_PATH)
+        for name, (restype, argtypes) in HERMITE_BLOCK_ENSEMBLE_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _hermite_block_ensemble_lib = handle
+    return _hermite_block_ensemble_lib
 
 
 def hermite_block_lib() -> ctypes.CDLL:
@@ -1210,6 +1262,157 @@ class HermiteBlockSystem:
 
     def get_levels(self) -> np.ndarray:
         return self._levels.download(np.empty(self.num_bodies, dtype=np.int32))
+
+    def synchronize(self) -> None:
+        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+def hermite_block_ensemble_plan(num_bodies: int, num_systems: int, num_active: int, dtype=np.float32) -> HermiteBlockEnsemblePlan:
+    """nb_hermite_block_ensemble_plan_*: the solo geometry of a block step of `num_active` of `num_bodies` bodies, and the grids of `num_systems` systems"""
+    p = HermiteBlockEnsemblePlan()
+    fn = getattr(hermite_block_ensemble_lib(), "nb_hermite_block_ensemble_plan_" + ("f32" if np.dtype(dtype) == np.float32 else "f64"))
+    check(fn(num_bodies, num_systems, num_active, ctypes.byref(p)), "nb_hermite_block_ensemble_plan")
+    return p
+
+
+def hermite_block_ensemble_workspace_bytes(num_bodies: int, num_systems: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(hermite_block_ensemble_lib().nb_hermite_block_ensemble_workspace_bytes(num_bodies, num_systems, np.dtype(dtype).itemsize, ctypes.byref(out)),
+          "nb_hermite_block_ensemble_workspace_bytes")
+    return out.value
+
+
+class HermiteBlockEnsemble:
+    """B independent systems of N bodies on the device, each stepped by the Hermite scheme with block time steps of
+    include/nbody_hip_hermite_block.h, all of them in the launches of one call (include/nbody_hip_hermite_block_ensemble.h).
+
+    The state (positions, velocities, accelerations, jerks, ticks, levels), one status record per system, the summary record and the
+    workspace are owned here; arrays go in and out as (B, N, 4), ticks and levels as (B, N).  ``set_state`` uploads positions
+    {x, y, z, m} and velocities; ``init`` evaluates and assigns the first levels; ``step(t_stop)`` enqueues one block step of every system
+    that has not reached t_stop; ``advance(t_stop, batch)`` enqueues batches of calls and one summary, reads 64 bytes, and repeats until
+    every system is stopped; ``summary()`` and ``statuses()`` read the device records; ``snapshot()`` is every system synchronised at its
+    own status time.  `params`: a HermiteBlockParams (default: eta 0.02, eta_start 0.01, dt_max 0.125, 30 levels); `softening_sq`: a
+    scalar or one value per system."""
+
+    def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, params=None, softening_sq=None):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies, self.num_systems = int(num_bodies), int(num_systems)
+        t = self.dtype.type
+        self.params = HermiteBlockParams(0.02, 0.01, 0.125, 30, 0) if params is None else params
+        self.tick = float(self.params.dt_max) * 2.0 ** -int(self.params.max_level)
+        self._workspace_bytes = hermite_block_ensemble_workspace_bytes(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
+        self.shape = (self.num_systems, self.num_bodies, 4)
+        count = self.num_bodies * self.num_systems
+        nbytes = 4 * count * self.dtype.itemsize
+        self._system_eps2 = None
+        self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out = (DeviceBuffer(nbytes) for _ in range(6))
+        self._ticks, self._levels = DeviceBuffer(8 * count), DeviceBuffer(4 * count)
+        self._status = DeviceBuffer(ctypes.sizeof(HermiteBlockStatus) * self.num_systems)
+        self._summary = DeviceBuffer(ctypes.sizeof(HermiteBlockEnsembleSummary))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+        softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else softening_sq
+        if np.ndim(softening_sq) == 0:
+            self.softening_sq = np.full(self.num_systems, softening_sq, self.dtype)
+        else:
+            self.softening_sq = np.ascontiguousarray(softening_sq, dtype=self.dtype)
+            if self.softening_sq.shape != (self.num_systems,):
+                self.free()
+                raise ValueError(f"softening_sq: a scalar or {self.num_systems} values")
+            self._system_eps2 = DeviceBuffer(self.softening_sq.nbytes)
+            self._system_eps2.upload(self.softening_sq)
+
+    def _buffers(self):
+        return [b for b in (self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out, self._ticks, self._levels, self._status, self._summary,
+                            self._workspace, self._system_eps2) if b is not None]
+
+    def _fn(self, name):
+        return getattr(hermite_block_ensemble_lib(), f"nb_hermite_block_ensemble_{name}_{self._suffix}")
+
+    def _state_args(self):
+        return (self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._levels.ptr, self._status.ptr, self._workspace.ptr,
+                self._workspace_bytes, self.num_bodies, self.num_systems, self._scalar(self.softening_sq[0]),
+                self._system_eps2.ptr if self._system_eps2 is not None else None, ctypes.byref(self.params))
+
+    def set_state(self, positions, velocities) -> None:
+        for buf, data in ((self._pos, positions), (self._vel, velocities)):
+            data = np.ascontiguousarray(data, dtype=self.dtype)
+            if data.shape != self.shape:
+                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
+            buf.upload(data)
+
+    def init(self, stream=None) -> None:
+        check(self._fn("init")(*self._state_args(), stream), "nb_hermite_block_ensemble_init")
+
+    def step(self, t_stop=float("inf"), stream=None) -> None:
+        check(self._fn("step")(*self._state_args(), float(t_stop), stream), "nb_hermite_block_ensemble_step")
+
+    def summary(self, stream=None) -> HermiteBlockEnsembleSummary:
+        """the status records folded on the device (one launch), then 64 bytes read"""
+        out = HermiteBlockEnsembleSummary()
+        check(hermite_block_ensemble_lib().nb_hermite_block_ensemble_summary(self._status.ptr, self.num_systems, self._summary.ptr, stream), "nb_hermite_block_ensemble_summary")
+        check(lib().nb_d2h(ctypes.byref(out), self._summary.ptr, ctypes.sizeof(out), stream), "nb_d2h(summary)")
+        return out
+
+    def statuses(self, stream=None):
+        """the B status records"""
+        out = (HermiteBlockStatus * self.num_systems)()
+        check(lib().nb_d2h(ctypes.byref(out), self._status.ptr, ctypes.sizeof(out), stream), "nb_d2h(status)")
+        return list(out)
+
+    def times(self) -> np.ndarray:
+        return np.array([s.now_ticks * self.tick for s in self.statuses()])
+
+    def advance(self, t_stop, batch: int = 64, stream=None) -> HermiteBlockEnsembleSummary:
+        """block steps until every system's next one would pass t_stop: `batch` calls and a summary are enqueued, then 64 bytes are read"""
+        while True:
+            for _ in range(batch):
+                self.step(t_stop, stream)
+            summary = self.summary(stream)
+            if summary.stopped == summary.systems:
+                return summary
+
+    def sync(self, stream=None) -> None:
+        """the synchronised snapshots, left on the device: snapshot_ptrs() for nb_energy_* (system s at byte offset s * 4 N sizeof T)"""
+        check(self._fn("sync")(self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._status.ptr,
+                               self.num_bodies, self.num_systems, ctypes.byref(self.params), stream), "nb_hermite_block_ensemble_sync")
+
+    def snapshot(self, stream=None):
+        """(positions, velocities) of every body predicted to its system's status time (nb_hermite_block_ensemble_sync_*)"""
+        self.sync(stream)
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+        return self._download(self._pos_out), self._download(self._vel_out)
+
+    def snapshot_ptrs(self):
+        return self._pos_out.ptr, self._vel_out.ptr
+
+    def _download(self, buf: DeviceBuffer) -> np.ndarray:
+        return buf.download(np.empty(self.shape, dtype=self.dtype))
+
+    def get_positions(self) -> np.ndarray:
+        return self._download(self._pos)
+
+    def get_velocities(self) -> np.ndarray:
+        return self._download(self._vel)
+
+    def get_accelerations(self) -> np.ndarray:
+        return self._download(self._acc)
+
+    def get_jerks(self) -> np.ndarray:
+        return self._download(self._jerk)
+
+    def get_ticks(self) -> np.ndarray:
+        return self._ticks.download(np.empty(self.shape[:2], dtype=np.uint64))
+
+    def get_levels(self) -> np.ndarray:
+        return self._levels.download(np.empty(self.shape[:2], dtype=np.int32))
 
     def synchronize(self) -> None:
         check(lib().nb_device_synchronize(), "nb_device_synchronize")

@@ -32,11 +32,7 @@ namespace {
 
 #include "hermite_body.h"
 
-__device__ __forceinline__ unsigned long long ticks_of(int level, int max_level) {
-    const int k = level < 0 ? 0 : (level > max_level ? max_level : level);
-    return 1ull << (max_level - k);
-}
-__device__ __forceinline__ double tick_length(const BlockParams& p) { return __builtin_ldexp(p.dt_max, -p.max_level); }
+#include "hermite_block_kernels_shared.h"
 
 template <typename T, int S>
 __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_block_eval(const T* state8, const unsigned* active, const BlockCtrl* ctrl, T* partial,
@@ -93,29 +89,6 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 }
 
 // ---- the schedule ---------------------------------------------------------------------------------------------------------------------
-
-struct MinLevel {
-    unsigned long long next;
-    int                level;
-};
-// the minimum of `next` and the maximum of `level` over a workgroup of 256
-__device__ __forceinline__ MinLevel block_fold(MinLevel m, unsigned long long* lds_next, int* lds_level) {
-    const int tid  = threadIdx.x;
-    lds_next[tid]  = m.next;
-    lds_level[tid] = m.level;
-    __syncthreads();
-#pragma unroll 1
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) {
-            const unsigned long long other = lds_next[tid + half];
-            if (other < lds_next[tid]) lds_next[tid] = other;
-            const int deeper = lds_level[tid + half];
-            if (deeper > lds_level[tid]) lds_level[tid] = deeper;
-        }
-        __syncthreads();
-    }
-    return MinLevel{lds_next[0], lds_level[0]};
-}
 
 __global__ __launch_bounds__(256) void block_min_partial(const unsigned long long* ticks, const int* levels, unsigned n, int max_level, unsigned long long* min_part, int* lvl_part) {
     __shared__ unsigned long long lds_next[256];
@@ -223,26 +196,6 @@ __global__ __launch_bounds__(256) void block_scatter(const unsigned long long* t
     unsigned at = offsets[blockIdx.x] + static_cast<unsigned>(__builtin_popcountll(mask & ((1ull << lane) - 1ull)));
     for (unsigned w = 0; w < wave; ++w) at += wave_count[w];
     active_list[at] = i;
-}
-
-__device__ __forceinline__ double norm3(double x, double y, double z) { return __builtin_sqrt(x * x + y * y + z * z); }
-
-// Aarseth's step from the stored T-typed a0, j0, a1, j1, in fp64 (include/nbody_hip_hermite_block.h)
-template <typename V> __device__ __forceinline__ double aarseth_dt(const V& a0, const V& j0, const V& a1, const V& j1, double h, double eta, double dt_max) {
-    const double d[3]  = {static_cast<double>(a0.x) - static_cast<double>(a1.x), static_cast<double>(a0.y) - static_cast<double>(a1.y), static_cast<double>(a0.z) - static_cast<double>(a1.z)};
-    const double p0[3] = {static_cast<double>(j0.x), static_cast<double>(j0.y), static_cast<double>(j0.z)};
-    const double p1[3] = {static_cast<double>(j1.x), static_cast<double>(j1.y), static_cast<double>(j1.z)};
-    double       a2e[3], a3[3];
-    const double h2 = h * h, h3 = h2 * h;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double a2 = (-6.0 * d[c] - h * (4.0 * p0[c] + 2.0 * p1[c])) / h2;
-        a3[c]           = (12.0 * d[c] + 6.0 * h * (p0[c] + p1[c])) / h3;
-        a2e[c]          = a2 + h * a3[c];
-    }
-    const double n_a1 = norm3(a1.x, a1.y, a1.z), n_j1 = norm3(p1[0], p1[1], p1[2]), n_a2 = norm3(a2e[0], a2e[1], a2e[2]), n_a3 = norm3(a3[0], a3[1], a3[2]);
-    const double dt = __builtin_sqrt(eta * (n_a1 * n_a2 + n_j1 * n_j1) / (n_j1 * n_a3 + n_a2 * n_a2));
-    return (dt == dt && dt - dt == 0) ? dt : dt_max;
 }
 
 template <typename T> __global__ __launch_bounds__(256) void hermite_block_finish(BlockArgs<T> a) {

@@ -1,0 +1,430 @@
+// hermite_block_ensemble.hip -- the kernels of libnbody_hip_hermite_block_ensemble.so (include/nbody_hip_hermite_block_ensemble.h): block
+// time steps (hermite_block.hip) of B independent systems of N bodies, one launch per stage whatever B is.  gfx950 only; FMA contraction on.
+//
+// One call is five launches, no atomics, every word written by one lane.  Workgroup g of a stage belongs to system g / (workgroups per
+// system) and never touches another system; each system has its own control record, `now`, active set and n_act in its own slice of the
+// workspace (hermite_block_ensemble_kernels.h):
+//   block_ensemble_min_partial    per workgroup of 256 bodies, the minimum of tick + ticks(level) (and the deepest level held)
+//   block_ensemble_predict_count  every workgroup folds its system's partials (<= 256) to the system's `now`; the system's first workgroup
+//                                 records it, decides about t_stop and writes the flag; every body is predicted to `now` into the system's
+//                                 slice of the workspace; active bodies are counted per workgroup
+//   block_ensemble_scatter        every workgroup adds the (<= 256) counts before its own, in index order, and writes its part of the
+//                                 active list, ascending body index; the system's first workgroup records n_act and the status counters
+//   hermite_block_ensemble_eval   the hot path, see below
+//   hermite_block_ensemble_finish one lane per active slot: J partials in range order, corrector, dt_A, new level, the body's stored state
+// The workgroups of a system whose step would pass t_stop leave after reading go = 0 from its control record; the other systems step.
+// (The solo library scans up to 65 536 counts in a launch of its own; with N <= 65 536 a system has at most 256 count blocks, which every
+// workgroup of the scatter adds itself.  Minima and integer sums are exact in any order: the schedule and the counters are the solo ones.)
+//
+// hermite_block_ensemble_eval<T, S> is hermite_block_eval (hermite_block.hip) per system: between a lane's bodies i and its six sums lies
+// the same TEXT (hermite_stream.inc with wave_groups.inc, wave_mates.inc and wave_fold.inc inside it), and (tile, range) come from
+// stream_geometry(N, n_act of THIS system, 64 W, kBlockTarget) and the workgroup's index within its system, on a per-system grid of
+// block_launch_groups(N, 64 W).  So tiles, J and with them the order of every sum are the solo step's, and the bits are.  A target that
+// shrank with B would save workgroups and partial planes but make a system's bits depend on B: not taken.  Only the bases of the system's
+// arrays, its control record and its softening^2 are fetched per system, wave-uniform, before the loops; the reference mass is the mass of
+// the system's first body (hermite_stream.inc reads it through the system's scalar-load pointer).
+#include "hermite_block_ensemble_kernels.h"
+
+namespace nb {
+namespace {
+
+#include "nbody_lane.h"
+
+#include "hermite_stream.h"
+
+#include "hermite_body.h"
+
+#include "hermite_block_kernels_shared.h"
+
+// softening^2 == 0: the floor of nbody_hip_hermite.h (the i = j term contributes 0, not NaN)
+template <typename T> __device__ __forceinline__ T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
+
+// (read-only for the whole launch -> a scalar load where the index is wave-uniform)
+template <typename V> __device__ __forceinline__ V uniform_load(const V* p, size_t index) {
+    typedef const V __attribute__((address_space(4)))* uniform_ptr;
+    return reinterpret_cast<uniform_ptr>(reinterpret_cast<unsigned long long>(p))[index];
+}
+
+// What the evaluation needs of a call: the workspace and where a system's sections lie in its slice of it.
+template <typename T> struct BlockEnsembleEvalArgs {
+    char*    workspace;
+    size_t   stride, state8, partial, active, ctrl;
+    const T* system_eps2;
+    T        eps2;
+    unsigned n, groups_per_system;
+};
+
+template <typename T, int S>
+__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) void hermite_block_ensemble_eval(BlockEnsembleEvalArgs<T> a) {
+    using LT         = Lane<T>;
+    using vec4       = typename LT::vec4;
+    using vec        = typename LT::vec;
+    using raw4       = typename LT::raw4;
+    using bits       = typename LT::bits;
+    constexpr int W      = LT::W;  // bodies i per lane
+    constexpr int U      = unroll_for<T>();
+    constexpr int STRIDE = 2;  // vec4 per body of state8
+    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx8 / x16
+
+    // the workgroup's system, and its index among that system's workgroups (wave-uniform: the whole workgroup leaves together)
+    const unsigned system = blockIdx.x / a.groups_per_system;
+    const unsigned local  = blockIdx.x - system * a.groups_per_system;
+    char* const    slice  = a.workspace + static_cast<size_t>(system) * a.stride;
+    const BlockCtrl* const ctrl = reinterpret_cast<const BlockCtrl*>(slice + a.ctrl);
+    if (ctrl->go == 0) return;
+    const unsigned  n     = a.n;
+    const unsigned  n_act = ctrl->n_act;
+    const BlockGeom geom  = stream_geometry(n, n_act, 64 * W, kBlockTarget);
+    if (local >= geom.tiles * geom.ranges) return;
+    const unsigned ranges = geom.ranges;
+    const unsigned tile   = local / ranges;
+    const unsigned range  = local % ranges;
+    const unsigned slots  = geom.tiles * (64 * W);
+
+    const T* const        state8  = reinterpret_cast<const T*>(slice + a.state8);
+    const unsigned* const active  = reinterpret_cast<const unsigned*>(slice + a.active);
+    T* const              partial = reinterpret_cast<T*>(slice + a.partial);
+    const T               eps2_system = floored(a.system_eps2 != nullptr ? uniform_load(a.system_eps2, system) : a.eps2);
+
+    const T* const   pos_base = state8;
+    const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state8));
+    const int        tid  = threadIdx.x;
+    const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int        lane = tid & 63;
+
+    // bodies i of this lane: slots tile_base + k*64 + lane of the system's active list
+    const unsigned tile_base = tile * (64 * W);
+    vec            px, py, pz, vx, vy, vz;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned slot = tile_base + k * 64 + lane;
+        const size_t   i    = active[slot < n_act ? slot : n_act - 1];
+        const vec4     p    = reinterpret_cast<const vec4*>(state8)[2 * i];
+        const vec4     v    = reinterpret_cast<const vec4*>(state8)[2 * i + 1];
+        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
+        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
+    }
+    vec eps2 = LT::splat(eps2_system);
+    LT::keep_in_vgpr(eps2);
+
+    auto body_j = [&](size_t j, BodyJ<T>& b) { b.p = jp[2 * j], b.v = jp[2 * j + 1]; };  // adjacent: one s_load_dwordx8 / x16
+#include "hermite_stream.inc"
+
+    // planes [J][6][slots] of this system: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) partial[(static_cast<size_t>(range) * 6 + q) * slots + tile_base + k * 64 + lane] = LT::get(second[q], k);
+    }
+}
+
+// ---- the schedule, per system -----------------------------------------------------------------------------------------------------------
+
+template <typename T> __device__ __forceinline__ char* slice_of(const BlockEnsembleArgs<T>& a, unsigned system) { return a.workspace + static_cast<size_t>(system) * a.layout.stride; }
+template <typename T> __device__ __forceinline__ BlockCtrl* ctrl_of(const BlockEnsembleArgs<T>& a, unsigned system) {
+    return reinterpret_cast<BlockCtrl*>(slice_of(a, system) + a.layout.ctrl);
+}
+
+// Per workgroup of 256 bodies, the minimum of tick + ticks(level) and the deepest level held -> the system's partial minima (<= 256).
+template <typename T> __global__ __launch_bounds__(256) void block_ensemble_min_partial(BlockEnsembleArgs<T> a) {
+    __shared__ unsigned long long lds_next[256];
+    __shared__ int                lds_level[256];
+    const unsigned                system = blockIdx.x / a.blocks;
+    const unsigned                block  = blockIdx.x - system * a.blocks;
+    const unsigned                local  = block * 256u + threadIdx.x;
+    MinLevel                      m{~0ull, 0};
+    if (local < a.n) {
+        const size_t i = static_cast<size_t>(system) * a.n + local;
+        m.level        = a.levels[i];
+        m.next         = a.ticks[i] + ticks_of(m.level, a.p.max_level);
+        m.level        = m.level > 0 ? m.level : 0;
+    }
+    m = block_fold(m, lds_next, lds_level);
+    if (threadIdx.x != 0) return;
+    char* const slice = slice_of(a, system);
+    reinterpret_cast<unsigned long long*>(slice + a.layout.min_part)[block] = m.next;
+    reinterpret_cast<int*>(slice + a.layout.lvl_part)[block]                = m.level;
+}
+
+// Every workgroup folds its system's partial minima (one per lane) to the system's `now` and decides about t_stop; the system's first
+// workgroup records both in the control record and the flag and deepest_level in the status record; every body of the system is predicted
+// to `now` into the workspace; active bodies are counted per workgroup.
+template <typename T> __global__ __launch_bounds__(256) void block_ensemble_predict_count(BlockEnsembleArgs<T> a) {
+    using vec4 = typename Lane<T>::vec4;
+    __shared__ unsigned long long lds_next[256];
+    __shared__ int                lds_level[256];
+    __shared__ unsigned           wave_count[4];
+    const unsigned                system = blockIdx.x / a.blocks;
+    const unsigned                block  = blockIdx.x - system * a.blocks;
+    char* const                   slice  = slice_of(a, system);
+    MinLevel                      m{~0ull, 0};
+    if (threadIdx.x < a.blocks) {
+        m.next  = reinterpret_cast<const unsigned long long*>(slice + a.layout.min_part)[threadIdx.x];
+        m.level = reinterpret_cast<const int*>(slice + a.layout.lvl_part)[threadIdx.x];
+    }
+    m                            = block_fold(m, lds_next, lds_level);
+    const unsigned long long now = m.next;
+    const double             q   = tick_length(a.p);
+    const bool               go  = static_cast<double>(now) * q <= a.t_stop;
+    if (block == 0 && threadIdx.x == 0) {
+        BlockCtrl* const   c = ctrl_of(a, system);
+        BlockStatus* const s = a.status + system;
+        c->now = now, c->go = go ? 1u : 0u;
+        if (!go) c->n_act = 0;
+        const unsigned flags = s->flags;
+        s->flags             = go ? (flags & ~kBlockStopped) : (flags | kBlockStopped);
+        const int deepest    = s->deepest_level;
+        s->deepest_level     = m.level > deepest ? m.level : deepest;
+    }
+    if (!go) return;
+    const unsigned local  = block * 256u + threadIdx.x;
+    bool           active = false;
+    if (local < a.n) {
+        const size_t             i    = static_cast<size_t>(system) * a.n + local;
+        const unsigned long long tick = a.ticks[i];
+        active                        = tick + ticks_of(a.levels[i], a.p.max_level) == now;
+        const T                  dt   = static_cast<T>(static_cast<double>(now - tick) * q);
+        const vec4 x = reinterpret_cast<const vec4*>(a.pos)[i], v = reinterpret_cast<const vec4*>(a.vel)[i];
+        const vec4 acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
+        vec4       xp, vp;
+        predict_body<T>(x, v, acc, jerk, dt, xp, vp);
+        vec4* const state8 = reinterpret_cast<vec4*>(slice + a.layout.state8);
+        state8[2 * static_cast<size_t>(local)]     = xp;
+        state8[2 * static_cast<size_t>(local) + 1] = vp;
+    }
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
+    __syncthreads();
+    if (threadIdx.x == 0) reinterpret_cast<unsigned*>(slice + a.layout.counts)[block] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+}
+
+// The scan and the scatter in one launch: a system has at most 256 counts, so every workgroup adds those before its own itself (integer
+// sums: the order changes nothing) and writes its active bodies behind them, ascending.  The counts are only read.  The system's first
+// workgroup adds all of them: n_act and the status counters, as block_scan records them.
+template <typename T> __global__ __launch_bounds__(256) void block_ensemble_scatter(BlockEnsembleArgs<T> a) {
+    __shared__ unsigned wave_count[4];
+    __shared__ unsigned before_part[4], all_part[4];
+    const unsigned      system = blockIdx.x / a.blocks;
+    const unsigned      block  = blockIdx.x - system * a.blocks;
+    BlockCtrl* const    c      = ctrl_of(a, system);
+    if (c->go == 0) return;
+    const unsigned long long now    = c->now;
+    const unsigned* const    counts = reinterpret_cast<const unsigned*>(slice_of(a, system) + a.layout.counts);
+    const unsigned           wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // lane t holds count t of the system
+    const unsigned mine   = threadIdx.x < a.blocks ? counts[threadIdx.x] : 0u;
+    unsigned       before = threadIdx.x < block ? mine : 0u, all = mine;
+#pragma unroll
+    for (int shift = 32; shift > 0; shift >>= 1) before += __shfl_xor(before, shift, 64), all += __shfl_xor(all, shift, 64);
+    const unsigned           local  = block * 256u + threadIdx.x;
+    const size_t             i      = static_cast<size_t>(system) * a.n + local;
+    const bool               active = local < a.n && a.ticks[i] + ticks_of(a.levels[i], a.p.max_level) == now;
+    const unsigned long long mask   = __builtin_amdgcn_ballot_w64(active);
+    if (lane == 0) wave_count[wave] = static_cast<unsigned>(__builtin_popcountll(mask)), before_part[wave] = before, all_part[wave] = all;
+    __syncthreads();
+    if (block == 0 && threadIdx.x == 0) {
+        const unsigned     n_act = all_part[0] + all_part[1] + all_part[2] + all_part[3];
+        BlockStatus* const s     = a.status + system;
+        c->n_act                 = n_act;
+        s->now_ticks             = now;
+        s->block_steps += 1;
+        s->body_steps += n_act;
+        s->last_active = n_act;
+    }
+    if (!active) return;
+    unsigned at = before_part[0] + before_part[1] + before_part[2] + before_part[3] + static_cast<unsigned>(__builtin_popcountll(mask & ((1ull << lane) - 1ull)));
+    for (unsigned w = 0; w < wave; ++w) at += wave_count[w];
+    reinterpret_cast<unsigned*>(slice_of(a, system) + a.layout.active)[at] = local;
+}
+
+template <typename T> __global__ __launch_bounds__(256) void hermite_block_ensemble_finish(BlockEnsembleArgs<T> a) {
+    using vec4 = typename Lane<T>::vec4;
+    constexpr unsigned per_tile = 64 * Lane<T>::W;
+    const unsigned     system = blockIdx.x / a.blocks;
+    const unsigned     block  = blockIdx.x - system * a.blocks;
+    const BlockCtrl*   c      = ctrl_of(a, system);
+    if (c->go == 0) return;
+    const unsigned n_act = c->n_act;
+    const unsigned slot  = block * 256u + threadIdx.x;
+    if (slot >= n_act) return;
+    const BlockGeom          geom   = stream_geometry(a.n, n_act, per_tile, kBlockTarget);
+    const size_t             slots  = static_cast<size_t>(geom.tiles) * per_tile;
+    const unsigned long long now    = c->now;
+    const char* const        slice  = slice_of(a, system);
+    const T* const           state8 = reinterpret_cast<const T*>(slice + a.layout.state8);
+    const size_t             i      = static_cast<size_t>(system) * a.n + reinterpret_cast<const unsigned*>(slice + a.layout.active)[slot];
+    // sum[6]: the J ranges' partial sums of this slot, in range order
+    constexpr int            NS      = 6;
+    const T* const           partial = reinterpret_cast<const T*>(slice + a.layout.partial);
+    const unsigned           ranges  = geom.ranges;
+#include "range_sum.inc"
+    const T m_first = state8[3];
+    const T m_ref   = usable_unit(m_first) ? m_first : T(1);
+    vec4    a1, j1;
+    a1.x = sum[0] * m_ref, a1.y = sum[1] * m_ref, a1.z = sum[2] * m_ref, a1.w = 0;
+    j1.x = sum[3] * m_ref, j1.y = sum[4] * m_ref, j1.z = sum[5] * m_ref, j1.w = 0;
+
+    int                      k     = a.levels[i];
+    k                              = k < 0 ? 0 : (k > a.p.max_level ? a.p.max_level : k);
+    const double             q     = tick_length(a.p);
+    const unsigned long long own   = 1ull << (a.p.max_level - k);
+    const double             dt_i  = static_cast<double>(own) * q;
+    const T                  dt    = static_cast<T>(dt_i);
+    // the corrector of nb_hermite_step_*, with the body's own dt
+    const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
+    vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
+    const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
+    const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
+#include "hermite_correct.inc"
+    reinterpret_cast<vec4*>(a.pos)[i]  = x1;
+    reinterpret_cast<vec4*>(a.vel)[i]  = v;
+    reinterpret_cast<vec4*>(a.acc)[i]  = a1;
+    reinterpret_cast<vec4*>(a.jerk)[i] = j1;
+
+    const double dt_a = aarseth_dt(a0, j0, a1, j1, dt_i, a.p.eta, a.p.dt_max);
+    if (dt_a < dt_i) {
+        while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > dt_a) ++k;
+    } else if (dt_a >= 2.0 * dt_i && k > 0 && now % (2 * own) == 0) {
+        --k;
+    }
+    a.levels[i] = k;
+    a.ticks[i]  = now;
+}
+
+// init: per system, levels from the accelerations and jerks the ensemble evaluation left, ticks 0, the status and control records cleared
+template <typename T> __global__ __launch_bounds__(256) void block_ensemble_init_levels(BlockEnsembleArgs<T> a) {
+    using vec4            = typename Lane<T>::vec4;
+    const unsigned system = blockIdx.x / a.blocks;
+    const unsigned local  = (blockIdx.x - system * a.blocks) * 256u + threadIdx.x;
+    if (local == 0) {
+        BlockStatus s{};
+        a.status[system] = s;
+        BlockCtrl c{};
+        *ctrl_of(a, system) = c;
+    }
+    if (local >= a.n) return;
+    const size_t i     = static_cast<size_t>(system) * a.n + local;
+    const vec4   acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
+    const double want0 = a.p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
+    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : a.p.dt_max;
+    const double q     = tick_length(a.p);
+    int          k     = 0;
+    while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > want) ++k;
+    a.levels[i] = k;
+    a.ticks[i]  = 0;
+}
+
+// every body predicted to ITS system's status time
+template <typename T>
+__global__ __launch_bounds__(256) void block_ensemble_sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const unsigned long long* ticks,
+                                                           const BlockStatus* status, unsigned n, unsigned blocks, BlockParams p) {
+    using vec4            = typename Lane<T>::vec4;
+    const unsigned system = blockIdx.x / blocks;
+    const unsigned local  = (blockIdx.x - system * blocks) * 256u + threadIdx.x;
+    if (local >= n) return;
+    const size_t             i   = static_cast<size_t>(system) * n + local;
+    const unsigned long long now = status[system].now_ticks, tick = ticks[i];
+    const T                  dt  = static_cast<T>(static_cast<double>(now > tick ? now - tick : 0ull) * tick_length(p));
+    const vec4 x = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i];
+    vec4       xp, vp;
+    predict_body<T>(x, v, reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i], dt, xp, vp);
+    vp.w                                 = v.w;
+    reinterpret_cast<vec4*>(pos_out)[i] = xp;
+    reinterpret_cast<vec4*>(vel_out)[i] = vp;
+}
+
+// The B status records folded into one: integer sums and exact minima / maxima, so the order changes nothing.  One workgroup.
+__global__ __launch_bounds__(256) void block_ensemble_summary(const BlockStatus* status, unsigned b, BlockEnsembleSummary* out) {
+    __shared__ unsigned long long lds[5][256];
+    __shared__ int                lds_level[256];
+    const int                     tid = threadIdx.x;
+    unsigned long long            lo = ~0ull, hi = 0, blocks = 0, bodies = 0, stopped = 0;
+    int                           deepest = 0;
+    for (unsigned s = tid; s < b; s += 256u) {
+        const BlockStatus r = status[s];
+        lo = r.now_ticks < lo ? r.now_ticks : lo, hi = r.now_ticks > hi ? r.now_ticks : hi;
+        blocks += r.block_steps, bodies += r.body_steps, stopped += (r.flags & kBlockStopped) ? 1 : 0;
+        deepest = r.deepest_level > deepest ? r.deepest_level : deepest;
+    }
+    lds[0][tid] = lo, lds[1][tid] = hi, lds[2][tid] = blocks, lds[3][tid] = bodies, lds[4][tid] = stopped, lds_level[tid] = deepest;
+    __syncthreads();
+#pragma unroll 1
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) {
+            if (lds[0][tid + half] < lds[0][tid]) lds[0][tid] = lds[0][tid + half];
+            if (lds[1][tid + half] > lds[1][tid]) lds[1][tid] = lds[1][tid + half];
+            lds[2][tid] += lds[2][tid + half], lds[3][tid] += lds[3][tid + half], lds[4][tid] += lds[4][tid + half];
+            if (lds_level[tid + half] > lds_level[tid]) lds_level[tid] = lds_level[tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    BlockEnsembleSummary r{};
+    r.min_now_ticks = lds[0][0], r.max_now_ticks = lds[1][0], r.block_steps = lds[2][0], r.body_steps = lds[3][0];
+    r.systems = b, r.stopped = static_cast<unsigned>(lds[4][0]), r.deepest_level = lds_level[0];
+    *out = r;
+}
+
+template <typename T, int S> hipError_t launch_eval_s(const BlockEnsembleArgs<T>& a, hipStream_t stream) {
+    BlockEnsembleEvalArgs<T> e{};
+    e.workspace = a.workspace, e.stride = a.layout.stride, e.state8 = a.layout.state8, e.partial = a.layout.partial, e.active = a.layout.active, e.ctrl = a.layout.ctrl;
+    e.system_eps2 = a.system_eps2, e.eps2 = a.eps2, e.n = a.n, e.groups_per_system = a.groups_per_system;
+    hipLaunchKernelGGL((hermite_block_ensemble_eval<T, S>), dim3(a.groups_per_system * a.b), dim3(64 * S), 0, stream, e);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+template <typename T> hipError_t launch_block_ensemble_init(const BlockEnsembleArgs<T>& a, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block_ensemble_init_levels<T>), dim3(a.blocks * a.b), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T> hipError_t launch_block_ensemble_step(const BlockEnsembleArgs<T>& a, hipStream_t stream) {
+    const unsigned grid = a.blocks * a.b;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block_ensemble_min_partial<T>), dim3(grid), dim3(256), 0, stream, a);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL((block_ensemble_predict_count<T>), dim3(grid), dim3(256), 0, stream, a);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL((block_ensemble_scatter<T>), dim3(grid), dim3(256), 0, stream, a);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipError_t err = hipErrorInvalidValue;
+    switch (block_waves(a.n)) {
+        case 1: err = launch_eval_s<T, 1>(a, stream); break;
+        case 2: err = launch_eval_s<T, 2>(a, stream); break;
+        case 4: err = launch_eval_s<T, 4>(a, stream); break;
+        case 8: err = launch_eval_s<T, 8>(a, stream); break;
+        default: break;
+    }
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((hermite_block_ensemble_finish<T>), dim3(grid), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block_ensemble_sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const unsigned long long* ticks, const BlockStatus* status,
+                                      unsigned n, unsigned b, const BlockParams& p, hipStream_t stream) {
+    const unsigned blocks = block_ensemble_blocks(n);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block_ensemble_sync<T>), dim3(blocks * b), dim3(256), 0, stream, pos_out, vel_out, pos, vel, acc, jerk, ticks, status, n, blocks, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_ensemble_summary(const BlockStatus* status, unsigned b, BlockEnsembleSummary* out, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(block_ensemble_summary, dim3(1), dim3(256), 0, stream, status, b, out);
+    return hipGetLastError();
+}
+
+template hipError_t launch_block_ensemble_init<float>(const BlockEnsembleArgs<float>&, hipStream_t);
+template hipError_t launch_block_ensemble_init<double>(const BlockEnsembleArgs<double>&, hipStream_t);
+template hipError_t launch_block_ensemble_step<float>(const BlockEnsembleArgs<float>&, hipStream_t);
+template hipError_t launch_block_ensemble_step<double>(const BlockEnsembleArgs<double>&, hipStream_t);
+template hipError_t launch_block_ensemble_sync<float>(float*, float*, const float*, const float*, const float*, const float*, const unsigned long long*, const BlockStatus*,
+                                                      unsigned, unsigned, const BlockParams&, hipStream_t);
+template hipError_t launch_block_ensemble_sync<double>(double*, double*, const double*, const double*, const double*, const double*, const unsigned long long*, const BlockStatus*,
+                                                       unsigned, unsigned, const BlockParams&, hipStream_t);
+
+}  // namespace nb

@@ -3,6 +3,7 @@
 
 #include "bodyensemblehip.hpp"
 #include "bodyensemblehip_hermite.hpp"
+#include "bodyensemblehip_hermite_block.hpp"
 #include "compute.hpp"
 #include "randomise_bodies.hpp"
 #include "text.hpp"
@@ -73,6 +74,55 @@ template <typename T> auto run_hermite_typed(const EnsembleRun& run, std::vector
     }
 }
 
+// --integrator=hermite-block-ensemble: dt_max = dt; --t-end=T (or --steps=K: T = K dt) runs every system to the last block step not past
+// T, batches of calls and one summary between reads of 64 bytes; --benchmark times `iterations` intervals of dt after one untimed;
+// interactions are counted as the status records count them: the sum of n_act * N over the systems.  --dump: the synchronised snapshots.
+template <typename T> auto run_block_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+    const auto   n = run.num_bodies, b = run.num_systems;
+    const double dt_max = static_cast<double>(static_cast<T>(run.params.time_step));
+    const T      softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
+    const auto   params = nb_hermite_block_params_t{run.eta, 0.01, dt_max, run.levels, 0};
+    auto         ensemble = BodyEnsembleHIPHermiteBlock<T>(n, b, softening_sq, params);
+    ensemble.set_state(pos, vel);
+    const auto report = [&](const char* what, const nb_hermite_block_ensemble_summary_t& from, const nb_hermite_block_ensemble_summary_t& to) {
+        const auto   body_steps  = to.body_steps - from.body_steps;
+        const double evaluations = static_cast<double>(body_steps) / static_cast<double>(n);
+        std::printf("%s%llu block steps, %llu body steps = %s evaluations of N^2 interactions in all, deepest level %d\n", what,
+                    static_cast<unsigned long long>(to.block_steps - from.block_steps), static_cast<unsigned long long>(body_steps), text::width3(static_cast<float>(evaluations)).c_str(),
+                    to.deepest_level);
+    };
+    if (run.benchmark) {
+        const auto warm = ensemble.advance(dt_max);  // (untimed, as Compute::run_benchmark)
+        HipEvent   begin, stop;
+        begin.record();
+        const auto end = ensemble.advance(static_cast<double>(1 + run.iterations) * dt_max);
+        stop.record();
+        stop.synchronize();
+        const float  milliseconds = HipEvent::elapsed_ms(begin, stop);
+        const double interactions = static_cast<double>(end.body_steps - warm.body_steps) * static_cast<double>(n);
+        std::printf("%zu bodies x %zu systems, hermite-block integrator, total time for %d intervals of dt_max: %s ms\n", n, b, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("= %s ms per interval\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
+        report("= ", warm, end);
+        std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
+        return;
+    }
+    const auto   none  = ensemble.summary();
+    const double t_end = run.t_end > 0.0 ? run.t_end : static_cast<double>(run.steps) * dt_max;
+    const auto   end   = t_end > 0.0 ? ensemble.advance(t_end) : none;
+    if (!run.dump.empty()) {
+        ensemble.sync();
+        ensemble.get_positions(pos);
+        ensemble.get_velocities(vel);
+        write_dump<T>(run, pos, vel);
+    }
+    auto steps = std::vector<unsigned long long>();
+    for (const auto& status : ensemble.statuses()) steps.push_back(status.block_steps);
+    std::sort(steps.begin(), steps.end());
+    std::printf("%zu bodies x %zu systems, hermite-block integrator, eta %g, %d levels, to t = %g: %u systems stopped\n", n, b, run.eta, run.levels, t_end, end.stopped);
+    std::printf("block steps per system: fewest %llu, median %llu, most %llu\n", steps.front(), steps[steps.size() / 2], steps.back());
+    report("", none, end);
+}
+
 template <typename T> auto run_typed(const EnsembleRun& run) -> void {
     const auto n = run.num_bodies, b = run.num_systems;
     std::vector<T> pos(4 * n * b), vel(4 * n * b);
@@ -89,6 +139,10 @@ template <typename T> auto run_typed(const EnsembleRun& run) -> void {
         for (std::size_t s = 0; s < b; ++s) {
             randomise_bodies<T>(run.config, std::span<T>(pos).subspan(4 * n * s, 4 * n), std::span<T>(vel).subspan(4 * n * s, 4 * n), scaled.cluster_scale, scaled.velocity_scale);
         }
+    }
+    if (run.block) {
+        run_block_typed<T>(run, pos, vel);
+        return;
     }
     if (run.hermite) {
         run_hermite_typed<T>(run, pos, vel);

@@ -1,5 +1,6 @@
 // ensemble_cli.hpp -- `nbody --systems=<B>`: B independent systems of --numbodies bodies stepped in one launch (BodyEnsembleHIP), or, with
-// --integrator=hermite-ensemble, by 4th-order Hermite steps with one dt for all or a time step per system (BodyEnsembleHIPHermite).
+// --integrator=hermite-ensemble, by 4th-order Hermite steps with one dt for all or a time step per system (BodyEnsembleHIPHermite), or,
+// with --integrator=hermite-block-ensemble, by block time steps, a step per BODY (BodyEnsembleHIPHermiteBlock).
 #pragma once
 
 #include "nbody_types.hpp"
@@ -19,7 +20,9 @@ struct EnsembleRun {
     std::filesystem::path dump;
     bool                  hermite = false;  // --integrator=hermite-ensemble
     double                t_end = 0.0;      // hermite: > 0 runs the adaptive form to this time (--t-end), else --steps fixed steps of params.time_step
-    double                eta = 0.02;       // hermite, adaptive: the accuracy parameter of the systems' time steps (--eta)
+    double                eta = 0.02;       // hermite, adaptive: the accuracy parameter of the systems' time steps (--eta); block: of the bodies'
+    bool                  block = false;    // --integrator=hermite-block-ensemble: dt_max = params.time_step; --t-end, or --steps=K intervals of dt_max
+    int                   levels = 30;      // block: the deepest level (--levels)
 };
 
 // Starts from the current rand() state (main has applied --seed): system 0 is the single-system start-up state (the same three

@@ -11,10 +11,12 @@
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
 //                     --integrator=hermite-ensemble --systems=<B> (... of B systems, a time step per system: libnbody_hip_hermite_ensemble.so)
+//                     --integrator=hermite-block-ensemble --systems=<B> (block time steps of B systems: libnbody_hip_hermite_block_ensemble.so)
 #include "ensemble_cli.hpp"
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
 #include "../../include/nbody_hip_hermite_block.h"
+#include "../../include/nbody_hip_hermite_block_ensemble.h"
 #include "../../include/nbody_hip_hermite_ensemble.h"
 #include "../../include/nbody_hip_knn.h"
 #include "../../include/nbody_hip_neighbour.h"
@@ -79,9 +81,10 @@ struct Options {
     bool                  hermite = false;  // --integrator=hermite or hermite-block (euler, the reference's step, is the default)
     bool                  hermite_block = false;  // --integrator=hermite-block
     bool                  hermite_ensemble = false;  // --integrator=hermite-ensemble (with --systems)
-    std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble)
-    std::optional<double> t_end;   // --t-end (hermite-ensemble)
-    std::optional<int>    levels;  // --levels (hermite-block)
+    bool                  hermite_block_ensemble = false;  // --integrator=hermite-block-ensemble (with --systems)
+    std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble, hermite-block-ensemble)
+    std::optional<double> t_end;   // --t-end (hermite-ensemble, hermite-block-ensemble)
+    std::optional<int>    levels;  // --levels (hermite-block, hermite-block-ensemble)
 };
 
 constexpr auto help_text = R"(The MI355X NBody hot path (drop-in for cuda-nbody's compute path).
@@ -142,6 +145,11 @@ Options:
   --t-end FLOAT               hermite-ensemble: run every system to this time (> 0) with a time step of its own, eta (--eta) times the
                               smallest |a| / |jerk| of the system, and print the systems done and stalled and the fewest, median and
                               most steps per system
+  --integrator=hermite-block-ensemble  with --systems (required; its restrictions apply, numbodies * systems at most 2^28): block time steps
+                              (hermite-block's scheme, --eta and --levels) of every system in the launches of one call, every system
+                              with its own time.  --t-end=T (or --steps=K: T = K * dt) runs every system to its last block step not
+                              past T; --dump writes every system synchronised at its own time, in --systems' format; --benchmark
+                              times intervals of dt and counts the sum of n_act * N over the systems
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
 
@@ -281,8 +289,11 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
         } else if (name == "integrator") {
             const auto v = take_value();
-            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite-block" || *v == "hermite-ensemble");
-            if (ok) options.hermite_ensemble = *v == "hermite-ensemble", options.hermite = *v != "euler" && !options.hermite_ensemble, options.hermite_block = *v == "hermite-block";
+            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble");
+            if (ok) {
+                options.hermite_ensemble = *v == "hermite-ensemble", options.hermite_block_ensemble = *v == "hermite-block-ensemble";
+                options.hermite = (*v == "hermite" || *v == "hermite-block"), options.hermite_block = *v == "hermite-block";
+            }
         } else if (name == "eta") {
             const auto v = take_value();
             ok           = v.has_value();
@@ -388,10 +399,18 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         if (options.mode == NB_MODE_STRICT) return error("--integrator=hermite-ensemble has no strict mode: there is no CPU reference arithmetic to reproduce");
         if (options.t_end && (options.benchmark || options.steps > 0)) return error("--t-end cannot be combined with --benchmark or --steps (it runs every system to that time)");
     }
-    if (options.t_end && !options.hermite_ensemble) return error("--t-end belongs to --integrator=hermite-ensemble");
+    if (options.hermite_block_ensemble) {
+        if (options.systems == 0) return error("--integrator=hermite-block-ensemble needs --systems (and an explicit --numbodies of at most 65536)");
+        if (options.numbodies * options.systems > NB_HERMITE_BLOCK_ENSEMBLE_MAX_TOTAL) return error("--integrator=hermite-block-ensemble: numbodies * systems must be at most 2^28");
+        if (options.mode == NB_MODE_STRICT) return error("--integrator=hermite-block-ensemble has no strict mode: there is no CPU reference arithmetic to reproduce");
+        if (options.t_end && (options.benchmark || options.steps > 0)) return error("--t-end cannot be combined with --benchmark or --steps (it runs every system to that time)");
+    }
+    if (options.t_end && !options.hermite_ensemble && !options.hermite_block_ensemble) return error("--t-end belongs to --integrator=hermite-ensemble");
 
-    // (--eta is hermite-ensemble's too; the message is the one the block integrator's users know)
-    if ((options.levels && !options.hermite_block) || (options.eta && !options.hermite_block && !options.hermite_ensemble)) return error("--eta and --levels belong to --integrator=hermite-block");
+    // (--eta is hermite-ensemble's too, and both are hermite-block-ensemble's; the message is the one the block integrator's users know)
+    if ((options.levels && !options.hermite_block && !options.hermite_block_ensemble) || (options.eta && !options.hermite_block && !options.hermite_ensemble && !options.hermite_block_ensemble)) {
+        return error("--eta and --levels belong to --integrator=hermite-block");
+    }
 
     // the reference prints this hint and the full help on every successful parse (nbody.cpp:315-316)
     std::printf("Run \" nbody - benchmark[-numbodies = <numBodies>] \" to measure performance\n");
@@ -449,6 +468,8 @@ auto main(int argc, char** argv) -> int {
             run.hermite     = cmd_options.hermite_ensemble;
             run.t_end       = cmd_options.t_end.value_or(0.0);
             run.eta         = cmd_options.eta.value_or(run.eta);
+            run.block       = cmd_options.hermite_block_ensemble;
+            run.levels      = cmd_options.levels.value_or(run.levels);
             run_ensemble(run);
             return 0;
         }

@@ -72,8 +72,8 @@
  * Limits.  1 <= N <= 65 536 (NB_HERMITE_ENSEMBLE_MAX_BODIES), B >= 1, N*B <= 2^28, and B * groups_per_system * block_threads <= 2^31, so
  * that a call is one launch per stage.  Above 65 536 bodies one system fills the chip by itself: nb_hermite_step_* is the call there.
  *
- * Not built: several tiny systems packed into one wave (N < 64 * bodies_per_lane leaves lanes idle); per-system body counts; block
- * time steps per system; sharded forms.
+ * Not built: several tiny systems packed into one wave (N < 64 * bodies_per_lane leaves lanes idle); per-system body counts; sharded
+ * forms.  (Block time steps per system are nbody_hip_hermite_block_ensemble.h.)
  *
  * Errors.  NB_ERR_INVALID_ARGUMENT, returned before any HIP call, for: a null pointer (but the optional ones); N, B or their products
  * out of range; an array, a parameter array of step or the workspace not aligned to 4*sizeof(T) (system_softening_sq, dt_out:
