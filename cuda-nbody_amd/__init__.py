@@ -30,6 +30,8 @@ LAB_LIB_PATH = os.environ.get("NBODY_HIP_LAB_LIB", os.path.join(HERE, "libnbody_
 ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_ensemble.so"))
 # 4th-order Hermite steps (include/nbody_hip_hermite.h) are a fourth library on the same terms, loaded by hermite_lib().
 HERMITE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_LIB", os.path.join(HERE, "libnbody_hip_hermite.so"))
+# 6th-order Hermite steps (include/nbody_hip_hermite6.h) are an eleventh, loaded by hermite6_lib().
+HERMITE6_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_LIB", os.path.join(HERE, "libnbody_hip_hermite6.so"))
 # Hermite steps with block time steps (include/nbody_hip_hermite_block.h) are a fifth, loaded by hermite_block_lib().
 HERMITE_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_LIB", os.path.join(HERE, "libnbody_hip_hermite_block.so"))
 # Nearest neighbours, potentials and neighbour lists (include/nbody_hip_neighbour.h) are a sixth, loaded by neighbour_lib().
@@ -268,6 +270,30 @@ HERMITE_SIGNATURES = {
 }
 
 
+# include/nbody_hip_hermite6.h: exported by libnbody_hip_hermite6.so, and nothing else is
+class Hermite6Plan(ctypes.Structure):
+    """nb_hermite6_plan_t: the geometry of the acceleration + jerk + snap kernel, a function of N and the precision"""
+    _fields_ = [("bodies_per_lane", ctypes.c_int), ("waves_per_group", ctypes.c_int), ("unroll", ctypes.c_int),
+                ("groups", ctypes.c_uint), ("block_threads", ctypes.c_uint), ("lds_bytes", ctypes.c_uint)]
+
+
+HERMITE6_MAX_BODIES = 1 << 26
+HERMITE6_TIMESTEP_SCRATCH_BYTES = 8192
+HERMITE6_SIGNATURES = {
+    "nb_hermite6_workspace_bytes": (_ci, [_cu, _cu, _P(_sz)]),
+    "nb_hermite6_plan_f32": (_ci, [_cu, _P(Hermite6Plan)]),
+    "nb_hermite6_plan_f64": (_ci, [_cu, _P(Hermite6Plan)]),
+    "nb_hermite6_eval_f32": (_ci, [_vp] * 7 + [_sz, _cu, _cf, _vp]),
+    "nb_hermite6_eval_f64": (_ci, [_vp] * 7 + [_sz, _cu, _cd, _vp]),
+    "nb_hermite6_init_f32": (_ci, [_vp] * 7 + [_sz, _cu, _cf, _vp]),
+    "nb_hermite6_init_f64": (_ci, [_vp] * 7 + [_sz, _cu, _cd, _vp]),
+    "nb_hermite6_step_f32": (_ci, [_vp] * 8 + [_sz, _cu, _cf, _cf, _vp]),
+    "nb_hermite6_step_f64": (_ci, [_vp] * 8 + [_sz, _cu, _cd, _cd, _vp]),
+    "nb_hermite6_timestep_f32": (_ci, [_vp] * 4 + [_cu, _cf, _vp, _vp, _sz, _vp]),
+    "nb_hermite6_timestep_f64": (_ci, [_vp] * 4 + [_cu, _cd, _vp, _vp, _sz, _vp]),
+}
+
+
 # include/nbody_hip_hermite_block.h: exported by libnbody_hip_hermite_block.so, and nothing else is
 class HermiteBlockParams(ctypes.Structure):
     """nb_hermite_block_params_t"""
@@ -468,6 +494,7 @@ _knn_lib = None
 _field_lib = None
 _ensemble_lib = None
 _hermite_lib = None
+_hermite6_lib = None
 _hermite_block_lib = None
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
 
@@ -529,6 +556,21 @@ def hermite_lib() -> ctypes.CDLL:
             fn.restype, fn.argtypes = restype, argtypes
         _hermite_lib = handle
     return _hermite_lib
+
+
+def hermite6_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite6.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    global _hermite6_lib
+    if _hermite6_lib is None:
+        if not os.path.exists(HERMITE6_LIB_PATH):
+            raise FileNotFoundError(f"{HERMITE6_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
+                                    "(or __graft_entry__.build()); there is no CPU fallback")
+        handle = ctypes.CDLL(HERMITE6_LIB_PATH)
+        for name, (restype, argtypes) in HERMITE6_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _hermite6_lib = handle
+    return _hermite6_lib
 
 
 def hermite_ensemble_lib() -> ctypes.CDLL:
@@ -1008,6 +1050,72 @@ class HermiteSystem:
     def free(self) -> None:
         for b in self._buffers():
             b.free()
+
+
+def hermite6_plan(num_bodies: int, dtype=np.float32) -> Hermite6Plan:
+    """nb_hermite6_plan_*: the geometry of the acceleration + jerk + snap kernel for `num_bodies` bodies"""
+    p = Hermite6Plan()
+    fn = hermite6_lib().nb_hermite6_plan_f32 if np.dtype(dtype) == np.float32 else hermite6_lib().nb_hermite6_plan_f64
+    check(fn(num_bodies, ctypes.byref(p)), "nb_hermite6_plan")
+    return p
+
+
+def hermite6_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
+    out = _sz(0)
+    check(hermite6_lib().nb_hermite6_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_hermite6_workspace_bytes")
+    return out.value
+
+
+class Hermite6System(HermiteSystem):
+    """One system of N bodies on the device, stepped by the 6th-order Hermite scheme of include/nbody_hip_hermite6.h.
+
+    HermiteSystem's arrays and methods plus the snaps and crackles.  ``eval`` is nb_hermite6_init_*: it fills the stored accelerations,
+    jerks and snaps from the stored state and zeroes the crackles (what starts a run); ``step(dt)`` takes one step;
+    ``suggested_dt(eta)`` reads Aarseth's eta sqrt(min (|a||s| + |j|^2) / (|j||c| + |s|^2)) of the stored derivatives back."""
+
+    def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self.num_bodies = int(num_bodies)
+        t = self.dtype.type
+        self.softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else t(softening_sq)
+        self._workspace_bytes = hermite6_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
+        self.shape = (self.num_bodies, 4)
+        nbytes = 4 * self.num_bodies * self.dtype.itemsize
+        self._pos, self._vel, self._acc, self._jerk, self._snap, self._crackle = (DeviceBuffer(nbytes) for _ in range(6))
+        self._workspace = DeviceBuffer(self._workspace_bytes)
+        self._scratch = DeviceBuffer(HERMITE6_TIMESTEP_SCRATCH_BYTES)
+        self._dt = DeviceBuffer(8)
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+
+    def _buffers(self):
+        return super()._buffers() + [self._snap, self._crackle]
+
+    def eval(self, stream=None) -> None:
+        fn = getattr(hermite6_lib(), "nb_hermite6_init_" + self._suffix)
+        check(fn(self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._pos.ptr, self._vel.ptr, self._workspace.ptr, self._workspace_bytes,
+                 self.num_bodies, self._scalar(self.softening_sq), stream), "nb_hermite6_init")
+
+    def step(self, delta_time, stream=None) -> None:
+        fn = getattr(hermite6_lib(), "nb_hermite6_step_" + self._suffix)
+        check(fn(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._workspace.ptr,
+                 self._workspace_bytes, self.num_bodies, self._scalar(delta_time), self._scalar(self.softening_sq), stream), "nb_hermite6_step")
+
+    def suggested_dt(self, eta, stream=None):
+        fn = getattr(hermite6_lib(), "nb_hermite6_timestep_" + self._suffix)
+        check(fn(self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self.num_bodies, self._scalar(eta), self._dt.ptr, self._scratch.ptr,
+                 HERMITE6_TIMESTEP_SCRATCH_BYTES, stream), "nb_hermite6_timestep")
+        out = np.empty(1, dtype=self.dtype)
+        check(lib().nb_d2h(out.ctypes.data_as(_vp), self._dt.ptr, out.nbytes, stream), "nb_d2h")
+        return out[0]
+
+    def get_snaps(self) -> np.ndarray:
+        return self._download(self._snap)
+
+    def get_crackles(self) -> np.ndarray:
+        return self._download(self._crackle)
 
 
 def hermite_ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> HermiteEnsemblePlan:

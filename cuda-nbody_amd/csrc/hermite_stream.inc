@@ -1,7 +1,7 @@
-// hermite_stream.inc -- everything the acceleration + jerk kernels share between loading their bodies i and storing their sums, as TEXT
-// included inside the kernel body (hermite_eval in hermite_eval.hip, hermite_block_eval in hermite_block.hip; no include guard): the
-// interaction, the streaming loops (wave_groups.inc), the chunk loop of a wave with its unit / mixed forms and two-level sums, SIMD-mate
-// priority (wave_mates.inc) and the fold of the S waves (wave_fold.inc).
+// hermite_stream.inc -- everything the Hermite evaluation kernels share between loading their bodies i and storing their sums, as TEXT
+// included inside the kernel body (hermite_eval in hermite_eval.hip, hermite_block_eval in hermite_block.hip, their ensemble forms, and
+// hermite6_eval in hermite6_eval.hip; no include guard): the interaction, the streaming loops (wave_groups.inc), the chunk loop of a wave
+// with its unit / mixed forms and two-level sums, SIMD-mate priority (wave_mates.inc) and the fold of the S waves (wave_fold.inc).
 //
 // The kernel defines before it: T, LT, vec, bits, W, U, S; n, tid, wave, lane; the lane's bodies i px, py, pz, vx, vy, vz; eps2; and
 //   range, ranges       the workgroup streams range `range` of the J = `ranges` contiguous ranges of the chunks of bodies j
@@ -10,7 +10,14 @@
 //   body_j(j, b)        the scalar loads of body j into b
 // It gets: m_ref and, in wave 0 alone (the other waves return inside), second[6]: ax ay az jx jy jz of the lane's bodies i over the
 // workgroup's chunks, in units of m_ref.
-    constexpr int NS  = 6;
+//
+// A kernel with another interaction defines HERMITE_STREAM_SUMS (the number of sums, NS) and HERMITE_STREAM_INTERACTION (the file that
+// holds its `compute`, in the shape of the one below) in front of the include, which undefines both; it gets second[NS].  Without them
+// the text is the acceleration + jerk kernels', token for token.
+#ifndef HERMITE_STREAM_SUMS
+#define HERMITE_STREAM_SUMS 6
+#endif
+    constexpr int NS  = HERMITE_STREAM_SUMS;
     constexpr int CH  = kChunk;
     constexpr int LPT = CH / 64;
     static_assert(CH % U == 0, "the streaming loop is unrolled by U");
@@ -49,6 +56,9 @@
         for (int u = 0; u < U; ++u) body_j(j0 + u, b[u]);
     };
 
+#ifdef HERMITE_STREAM_INTERACTION
+#include HERMITE_STREAM_INTERACTION
+#else
     // UB bodies j against the lane's vector of bodies i, written stage by stage: UB independent chains in flight.  (wave_groups.inc passes
     // the index of the first; nothing here depends on it.)
     auto compute = [&]<bool UNIT, int UB>(const BodyJ<T>* b, unsigned, vec (&sum)[NS]) {
@@ -79,6 +89,7 @@
             sum[3] = LT::fma(ex[u], k3[u], sum[3]), sum[4] = LT::fma(ey[u], k3[u], sum[4]), sum[5] = LT::fma(ez[u], k3[u], sum[5]);
         }
     };
+#endif
 #include "wave_groups.inc"
     T    pending_scale = T(1);  // what `first` is still to be multiplied by
     auto flush         = [&]() {
@@ -132,3 +143,5 @@
     flush();
 
 #include "wave_fold.inc"
+#undef HERMITE_STREAM_SUMS
+#undef HERMITE_STREAM_INTERACTION

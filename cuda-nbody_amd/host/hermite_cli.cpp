@@ -1,7 +1,8 @@
-// hermite_cli.cpp -- `nbody --integrator=hermite` (hermite_cli.hpp)
+// hermite_cli.cpp -- `nbody --integrator=hermite`, `hermite6` and `hermite-block` (hermite_cli.hpp)
 #include "hermite_cli.hpp"
 
 #include "bodysystemhip_hermite.hpp"
+#include "bodysystemhip_hermite6.hpp"
 #include "bodysystemhip_hermite_block.hpp"
 #include "compute.hpp"
 #include "field_cli.hpp"
@@ -149,14 +150,27 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
     report_field_points();
 }
 
-template <typename T> auto run_typed(const HermiteRun& run) -> void {
+// what --benchmark prints of a scheme: its name, the flops of one interaction as its library evaluates it, and what the interaction returns
+struct Scheme {
+    const char* name;
+    int         flops;
+    const char* interaction;
+};
+// an acceleration + jerk interaction: 3 + 3 subtractions, 2 x 5 for r.r + eps^2 and r.w, rsqrt (4, the reference's convention), 2 + 1
+// products for s^-2, s^-3 and the mass, 2 for -3 (r.w) s^-2, 6 + 12 for the two sums
+constexpr Scheme kHermite4{"hermite", 43, "acceleration + jerk"};
+// an acceleration + jerk + snap interaction, counted the same way: 9 subtractions, 5 + 5 + 11 for r.r + eps^2, r.w and w.w + r.b, rsqrt (4),
+// 2 + 1 products for s^-2, s^-3 and the mass, 7 for alpha, beta and their multiples by -3 and -6, 6 + 12 + 18 for the three sums
+constexpr Scheme kHermite6{"hermite6", 80, "acceleration + jerk + snap"};
+
+template <typename T, typename System> auto run_typed(const HermiteRun& run, const Scheme& scheme) -> void {
     const auto     n = run.num_bodies;
     std::vector<T> pos(4 * n), vel(4 * n);
     startup_state<T>(run, pos, vel);
     // BodySystemHIP's conversions: dt float -> T, softening^2 = T(s) * T(s)
     const T dt = static_cast<T>(run.params.time_step);
     const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
-    auto system = BodySystemHIPHermite<T>(n, softening_sq);
+    auto system = System(n, softening_sq);
     system.set_state(pos, vel);
     const auto measure = run.energy && (run.benchmark || run.steps > 0);
     nb_energy_t start{};
@@ -194,14 +208,12 @@ template <typename T> auto run_typed(const HermiteRun& run) -> void {
         const float milliseconds = HipEvent::elapsed_ms(begin, stop);
         const float frequency    = static_cast<float>(run.iterations) * (1000.0f / milliseconds);
         const float interactions = static_cast<float>(static_cast<double>(n) * static_cast<double>(n) * 1e-9) * frequency;
-        // an acceleration + jerk interaction as this library evaluates it: 3 + 3 subtractions, 2 x 5 for r.r + eps^2 and r.w, rsqrt (4,
-        // the reference's convention), 2 + 1 products for s^-2, s^-3 and the mass, 2 for -3 (r.w) s^-2, 6 + 12 for the two sums
-        const int flops = 43;
-        std::printf("%zu bodies, hermite integrator, total time for %d iterations: %s ms\n", n, run.iterations, text::width3(milliseconds).c_str());
+        const int flops = scheme.flops;
+        std::printf("%zu bodies, %s integrator, total time for %d iterations: %s ms\n", n, scheme.name, run.iterations, text::width3(milliseconds).c_str());
         std::printf("= %s ms per step\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
         std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
-        std::printf("= %s %s-precision GFLOP/s at %d flops per acceleration + jerk interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
-                    sizeof(T) == 8 ? "double" : "single", flops);
+        std::printf("= %s %s-precision GFLOP/s at %d flops per %s interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
+                    sizeof(T) == 8 ? "double" : "single", flops, scheme.interaction);
         report_energy(1 + static_cast<std::size_t>(run.iterations));
         report_neighbourhood();
         report_field_points();
@@ -226,5 +238,9 @@ auto run_hermite(const HermiteRun& run) -> void {
         if (run.fp64) run_block_typed<double>(run); else run_block_typed<float>(run);
         return;
     }
-    if (run.fp64) run_typed<double>(run); else run_typed<float>(run);
+    if (run.sixth) {
+        if (run.fp64) run_typed<double, BodySystemHIPHermite6<double>>(run, kHermite6); else run_typed<float, BodySystemHIPHermite6<float>>(run, kHermite6);
+        return;
+    }
+    if (run.fp64) run_typed<double, BodySystemHIPHermite<double>>(run, kHermite4); else run_typed<float, BodySystemHIPHermite<float>>(run, kHermite4);
 }

@@ -1,5 +1,6 @@
 // hermite_cli.hpp -- `nbody --integrator=hermite`: the single-system run stepped by the 4th-order Hermite scheme (BodySystemHIPHermite),
-// and `nbody --integrator=hermite-block`: the same run with block time steps (BodySystemHIPHermiteBlock).
+// `nbody --integrator=hermite6`: the same run stepped by the 6th-order scheme (BodySystemHIPHermite6), and
+// `nbody --integrator=hermite-block`: the 4th-order run with block time steps (BodySystemHIPHermiteBlock).
 #pragma once
 
 #include "nbody_types.hpp"
@@ -21,6 +22,7 @@ struct HermiteRun {
     unsigned              knn = 0;  // --knn=<K> (0: not asked for): report_knn of the final state
     double                neighbours = -1.0;  // --neighbours=<radius> (< 0: not asked for): report_neighbours of the final state
     std::vector<double>   field_points;  // --field=<file>: x y z of every point (empty: not asked for): report_field of the final state
+    bool                  sixth = false;  // --integrator=hermite6: the 6th-order scheme (never with `block`)
     bool                  block = false;  // --integrator=hermite-block: dt_max = the demo row's dt, `steps` / `iterations` count intervals of dt_max
     double                eta = 0.02;     // --eta (the first steps use eta_start = 0.01)
     int                   levels = 30;    // --levels: steps down to dt_max * 2^-levels

@@ -9,12 +9,14 @@
 //                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --neighbours=<radius>  --knn=<K>  --field=<file>  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
+//                     --integrator=hermite6 (6th-order Hermite steps: libnbody_hip_hermite6.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
 //                     --integrator=hermite-ensemble --systems=<B> (... of B systems, a time step per system: libnbody_hip_hermite_ensemble.so)
 //                     --integrator=hermite-block-ensemble --systems=<B> (block time steps of B systems: libnbody_hip_hermite_block_ensemble.so)
 #include "ensemble_cli.hpp"
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
+#include "../../include/nbody_hip_hermite6.h"
 #include "../../include/nbody_hip_hermite_block.h"
 #include "../../include/nbody_hip_hermite_block_ensemble.h"
 #include "../../include/nbody_hip_hermite_ensemble.h"
@@ -80,6 +82,7 @@ struct Options {
     std::size_t           systems = 0;  // --systems=<B>: an ensemble of B systems (0: one system, the reference's run)
     bool                  hermite = false;  // --integrator=hermite or hermite-block (euler, the reference's step, is the default)
     bool                  hermite_block = false;  // --integrator=hermite-block
+    bool                  hermite6 = false;  // --integrator=hermite6 (`hermite` is set too: its restrictions and messages apply)
     bool                  hermite_ensemble = false;  // --integrator=hermite-ensemble (with --systems)
     bool                  hermite_block_ensemble = false;  // --integrator=hermite-block-ensemble (with --systems)
     std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble, hermite-block-ensemble)
@@ -139,6 +142,8 @@ Options:
                               body steps by its own dt * 2^-level, --steps=K advances to K * dt, interactions are counted as n_act * N
   --eta FLOAT [0.02]          hermite-block: accuracy parameter of the bodies' time steps (the first steps use 0.01)
   --levels UINT [30]          hermite-block: the deepest level, 0 to 40 (time steps down to dt * 2^-levels)
+  --integrator=hermite6       hermite's run and restrictions with the 6th-order scheme: acceleration, jerk and snap per interaction, the
+                              global error falls with dt^6
   --integrator=hermite-ensemble  with --systems (required; its restrictions apply, numbodies * systems at most 2^28): Hermite steps of every
                               system in one launch per stage.  --steps=K takes K steps of --integrator=hermite's dt, --dump writes in
                               --systems' format, --benchmark counts B*N^2 acceleration + jerk interactions per step
@@ -289,10 +294,10 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
         } else if (name == "integrator") {
             const auto v = take_value();
-            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble");
+            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite6" || *v == "hermite-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble");
             if (ok) {
                 options.hermite_ensemble = *v == "hermite-ensemble", options.hermite_block_ensemble = *v == "hermite-block-ensemble";
-                options.hermite = (*v == "hermite" || *v == "hermite-block"), options.hermite_block = *v == "hermite-block";
+                options.hermite = (*v == "hermite" || *v == "hermite6" || *v == "hermite-block"), options.hermite_block = *v == "hermite-block", options.hermite6 = *v == "hermite6";
             }
         } else if (name == "eta") {
             const auto v = take_value();
@@ -490,6 +495,7 @@ auto main(int argc, char** argv) -> int {
             run.knn        = cmd_options.knn.value_or(0u);
             run.field_points = cmd_options.field_points;
             run.block      = cmd_options.hermite_block;
+            run.sixth      = cmd_options.hermite6;
             run.eta        = cmd_options.eta.value_or(run.eta);
             run.levels     = cmd_options.levels.value_or(run.levels);
             run_hermite(run);
