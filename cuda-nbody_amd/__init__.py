@@ -487,15 +487,7 @@ HERMITE_BLOCK_ENSEMBLE_SIGNATURES = {
 }
 
 _lib = None
-_hermite_block_ensemble_lib = None
-_hermite_ensemble_lib = None
-_neighbour_lib = None
-_knn_lib = None
-_field_lib = None
-_ensemble_lib = None
-_hermite_lib = None
-_hermite6_lib = None
-_hermite_block_lib = None
+_loaded = {}  # path -> the library at that path, its signatures set
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
 
 
@@ -512,155 +504,71 @@ def is_lab() -> bool:
     return _lab
 
 
-def lib() -> ctypes.CDLL:
-    """Load libnbody_hip.so -- or, after use_lab(), libnbody_hip_lab.so (fails loudly when the HIP extension has not been built)."""
-    global _lib
-    if _lib is None:
-        path = LAB_LIB_PATH if _lab else LIB_PATH
+def _load(path: str, signatures: dict) -> ctypes.CDLL:
+    """The library at `path`, loaded once, every function of `signatures` given its types (fails loudly when it has not been built)."""
+    if path not in _loaded:
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
                                     "(or __graft_entry__.build()); there is no CPU fallback")
         handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in {**SIGNATURES, **TUNING_SIGNATURES, **(LAB_SIGNATURES if _lab else {})}.items():
+        for name, (restype, argtypes) in signatures.items():
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = restype, argtypes
-        _lib = handle
+        _loaded[path] = handle
+    return _loaded[path]
+
+
+def lib() -> ctypes.CDLL:
+    """Load libnbody_hip.so -- or, after use_lab(), libnbody_hip_lab.so (fails loudly when the HIP extension has not been built)."""
+    global _lib
+    if _lib is None:
+        _lib = _load(LAB_LIB_PATH if _lab else LIB_PATH, {**SIGNATURES, **TUNING_SIGNATURES, **(LAB_SIGNATURES if _lab else {})})
     return _lib
 
 
 def ensemble_lib() -> ctypes.CDLL:
     """Load libnbody_hip_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _ensemble_lib
-    if _ensemble_lib is None:
-        if not os.path.exists(ENSEMBLE_LIB_PATH):
-            raise FileNotFoundError(f"{ENSEMBLE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(ENSEMBLE_LIB_PATH)
-        for name, (restype, argtypes) in ENSEMBLE_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _ensemble_lib = handle
-    return _ensemble_lib
+    return _load(ENSEMBLE_LIB_PATH, ENSEMBLE_SIGNATURES)
 
 
 def hermite_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _hermite_lib
-    if _hermite_lib is None:
-        if not os.path.exists(HERMITE_LIB_PATH):
-            raise FileNotFoundError(f"{HERMITE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(HERMITE_LIB_PATH)
-        for name, (restype, argtypes) in HERMITE_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _hermite_lib = handle
-    return _hermite_lib
+    return _load(HERMITE_LIB_PATH, HERMITE_SIGNATURES)
 
 
 def hermite6_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite6.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _hermite6_lib
-    if _hermite6_lib is None:
-        if not os.path.exists(HERMITE6_LIB_PATH):
-            raise FileNotFoundError(f"{HERMITE6_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(HERMITE6_LIB_PATH)
-        for name, (restype, argtypes) in HERMITE6_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _hermite6_lib = handle
-    return _hermite6_lib
+    return _load(HERMITE6_LIB_PATH, HERMITE6_SIGNATURES)
 
 
 def hermite_ensemble_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _hermite_ensemble_lib
-    if _hermite_ensemble_lib is None:
-        if not os.path.exists(HERMITE_ENSEMBLE_LIB_PATH):
-            raise FileNotFoundError(f"{HERMITE_ENSEMBLE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(HERMITE_ENSEMBLE_LIB_PATH)
-        for name, (restype, argtypes) in HERMITE_ENSEMBLE_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _hermite_ensemble_lib = handle
-    return _hermite_ensemble_lib
+    return _load(HERMITE_ENSEMBLE_LIB_PATH, HERMITE_ENSEMBLE_SIGNATURES)
 
 
 def hermite_block_ensemble_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite_block_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _hermite_block_ensemble_lib
-    if _hermite_block_ensemble_lib is None:
-        if not os.path.exists(HERMITE_BLOCK_ENSEMBLE_LIB_PATH):
-            raise FileNotFoundError(f"{HERMITE_BLOCK_ENSEMBLE_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(HERMITE_BLOCK_ENSEMBLE_LIB_PATH)
-        for name, (restype, argtypes) in HERMITE_BLOCK_ENSEMBLE_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _hermite_block_ensemble_lib = handle
-    return _hermite_block_ensemble_lib
+    return _load(HERMITE_BLOCK_ENSEMBLE_LIB_PATH, HERMITE_BLOCK_ENSEMBLE_SIGNATURES)
 
 
 def hermite_block_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite_block.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _hermite_block_lib
-    if _hermite_block_lib is None:
-        if not os.path.exists(HERMITE_BLOCK_LIB_PATH):
-            raise FileNotFoundError(f"{HERMITE_BLOCK_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(HERMITE_BLOCK_LIB_PATH)
-        for name, (restype, argtypes) in HERMITE_BLOCK_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _hermite_block_lib = handle
-    return _hermite_block_lib
+    return _load(HERMITE_BLOCK_LIB_PATH, HERMITE_BLOCK_SIGNATURES)
 
 
 def neighbour_lib() -> ctypes.CDLL:
     """Load libnbody_hip_neighbour.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _neighbour_lib
-    if _neighbour_lib is None:
-        if not os.path.exists(NEIGHBOUR_LIB_PATH):
-            raise FileNotFoundError(f"{NEIGHBOUR_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(NEIGHBOUR_LIB_PATH)
-        for name, (restype, argtypes) in NEIGHBOUR_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _neighbour_lib = handle
-    return _neighbour_lib
+    return _load(NEIGHBOUR_LIB_PATH, NEIGHBOUR_SIGNATURES)
 
 
 def field_lib() -> ctypes.CDLL:
     """Load libnbody_hip_field.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _field_lib
-    if _field_lib is None:
-        if not os.path.exists(FIELD_LIB_PATH):
-            raise FileNotFoundError(f"{FIELD_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(FIELD_LIB_PATH)
-        for name, (restype, argtypes) in FIELD_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _field_lib = handle
-    return _field_lib
+    return _load(FIELD_LIB_PATH, FIELD_SIGNATURES)
 
 
 def knn_lib() -> ctypes.CDLL:
     """Load libnbody_hip_knn.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
-    global _knn_lib
-    if _knn_lib is None:
-        if not os.path.exists(KNN_LIB_PATH):
-            raise FileNotFoundError(f"{KNN_LIB_PATH} not found: build it with `make -C {os.path.join(HERE, 'csrc')}` "
-                                    "(or __graft_entry__.build()); there is no CPU fallback")
-        handle = ctypes.CDLL(KNN_LIB_PATH)
-        for name, (restype, argtypes) in KNN_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _knn_lib = handle
-    return _knn_lib
+    return _load(KNN_LIB_PATH, KNN_SIGNATURES)
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -743,6 +651,108 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+def _plan(load, stem: str, record, dtype, *sizes):
+    """nb_<stem>_plan_f32 / _f64 of the library `load()` gives, for `sizes`: a filled `record`"""
+    p = record()
+    fn = getattr(load(), f"nb_{stem}_plan_" + ("f32" if np.dtype(dtype) == np.float32 else "f64"))
+    check(fn(*sizes, ctypes.byref(p)), f"nb_{stem}_plan")
+    return p
+
+
+def _query_workspace_bytes(load, stem: str, dtype, *sizes) -> int:
+    """nb_<stem>_workspace_bytes of the library `load()` gives, for `sizes` and the precision"""
+    out = _sz(0)
+    check(getattr(load(), f"nb_{stem}_workspace_bytes")(*sizes, np.dtype(dtype).itemsize, ctypes.byref(out)), f"nb_{stem}_workspace_bytes")
+    return out.value
+
+
+class _DeviceState:
+    """What the classes of the small libraries share: a precision, the device buffers ``_buffers()`` lists, and the f32 / f64 entry
+    points of one library (``_library``: its loader; ``_prefix``: how its symbols begin)."""
+
+    _library, _prefix = None, "nb_"
+
+    def __init__(self, dtype):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64")
+        self._scalar = np.float32 if self.dtype == np.float32 else float
+        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+
+    def _fn(self, name: str):
+        return getattr(self._library(), f"{self._prefix}{name}_{self._suffix}")
+
+    def _call(self, name: str, *args) -> None:
+        check(self._fn(name)(*args), self._prefix + name)
+
+    def _device(self, data, own: DeviceBuffer, shape, dtype=None):
+        """the device address of `data`: its own when it is one, else a host array uploaded into `own`"""
+        if isinstance(data, DeviceBuffer):
+            return data.ptr
+        if isinstance(data, (int, ctypes.c_void_p)):
+            return data
+        host = np.ascontiguousarray(data, dtype=dtype or self.dtype)
+        if host.shape != shape:
+            raise ValueError(f"expected an array of shape {shape}, got {host.shape}")
+        own.upload(host)
+        return own.ptr
+
+    def _download(self, buf: DeviceBuffer) -> np.ndarray:
+        return buf.download(np.empty(self.shape, dtype=self.dtype))
+
+    def synchronize(self) -> None:
+        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+
+    def free(self) -> None:
+        for b in self._buffers():
+            b.free()
+
+
+class _HermiteState(_DeviceState):
+    """... and what the four Hermite classes share on top: positions, velocities, accelerations and jerks of ``shape``, and softening^2."""
+
+    def _softening_or_default(self, value):
+        """None: 0.01, BodySystemHIP's default (T(0.1) * T(0.1))"""
+        t = self.dtype.type
+        return t(np.float32(0.1)) * t(np.float32(0.1)) if value is None else value
+
+    def _set_system_softening(self, softening_sq) -> None:
+        """`softening_sq` a scalar or one value per system: ``softening_sq`` (B values) and, for the latter, their device copy"""
+        softening_sq = self._softening_or_default(softening_sq)
+        if np.ndim(softening_sq) == 0:
+            self.softening_sq = np.full(self.num_systems, softening_sq, self.dtype)
+        else:
+            self.softening_sq = np.ascontiguousarray(softening_sq, dtype=self.dtype)
+            if self.softening_sq.shape != (self.num_systems,):
+                self.free()
+                raise ValueError(f"softening_sq: a scalar or {self.num_systems} values")
+            self._system_eps2 = DeviceBuffer(self.softening_sq.nbytes)
+            self._system_eps2.upload(self.softening_sq)
+
+    def _softening(self):
+        """(softening_sq, system_softening_sq) as the ensemble calls take them"""
+        return self._scalar(self.softening_sq[0]), (self._system_eps2.ptr if self._system_eps2 is not None else None)
+
+    def set_state(self, positions, velocities) -> None:
+        for buf, data in ((self._pos, positions), (self._vel, velocities)):
+            data = np.ascontiguousarray(data, dtype=self.dtype)
+            if data.shape != self.shape:
+                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
+            buf.upload(data)
+
+    def get_positions(self) -> np.ndarray:
+        return self._download(self._pos)
+
+    def get_velocities(self) -> np.ndarray:
+        return self._download(self._vel)
+
+    def get_accelerations(self) -> np.ndarray:
+        return self._download(self._acc)
+
+    def get_jerks(self) -> np.ndarray:
+        return self._download(self._jerk)
 
 
 def integrate_nbody_system(new_positions, old_positions, velocities, current_read: int, delta_time, damping,
@@ -887,22 +897,19 @@ class BodySystemHIP:
 
 def ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> EnsemblePlan:
     """nb_ensemble_plan_*: the FAST geometry of `num_systems` systems of `num_bodies` bodies"""
-    p = EnsemblePlan()
-    fn = ensemble_lib().nb_ensemble_plan_f32 if np.dtype(dtype) == np.float32 else ensemble_lib().nb_ensemble_plan_f64
-    check(fn(num_bodies, num_systems, ctypes.byref(p)), "nb_ensemble_plan")
-    return p
+    return _plan(ensemble_lib, "ensemble", EnsemblePlan, dtype, num_bodies, num_systems)
 
 
-class BodyEnsembleHIP:
+class BodyEnsembleHIP(_DeviceState):
     """B independent systems of N bodies on the device, stepped together by nb_ensemble_integrate_* (include/nbody_hip_ensemble.h).
 
     Two ping-pong position arrays + one velocity array of 4*N*B T; system s holds bodies [s*N, (s+1)*N).  Positions and velocities go
     in and out as (B, N, 4) arrays; ``update`` writes pos[1-read] from pos[read] and swaps; ``set_*`` resets read = 0."""
 
+    _library, _prefix = staticmethod(ensemble_lib), "nb_ensemble_"
+
     def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, mode: int = NB_MODE_FAST):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies, self.num_systems, self.mode = int(num_bodies), int(num_systems), mode
         ensemble_plan(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses, before anything is allocated
         self.shape = (self.num_systems, self.num_bodies, 4)
@@ -927,10 +934,10 @@ class BodyEnsembleHIP:
         self._upload(self._vel, data)
 
     def get_positions(self) -> np.ndarray:
-        return self._pos[self.current_read].download(np.empty(self.shape, dtype=self.dtype))
+        return self._download(self._pos[self.current_read])
 
     def get_velocities(self) -> np.ndarray:
-        return self._vel.download(np.empty(self.shape, dtype=self.dtype))
+        return self._download(self._vel)
 
     def update(self, delta_time, damping=1.0, softening_sq=None, params=None, stream=None) -> None:
         """One step of every system.  `params`: None (every system uses delta_time, damping, softening_sq) or a (B, 4) array of
@@ -947,37 +954,28 @@ class BodyEnsembleHIP:
             if self._params is None:
                 self._params = DeviceBuffer(table.nbytes)
             self._params.upload(table)
-        fn = ensemble_lib().nb_ensemble_integrate_f32 if self.dtype == np.float32 else ensemble_lib().nb_ensemble_integrate_f64
-        scalar = np.float32 if self.dtype == np.float32 else float
-        check(fn(self._pos[1 - self.current_read].ptr, self._pos[self.current_read].ptr, self._vel.ptr, self.num_bodies, self.num_systems,
-                 scalar(delta_time), scalar(damping), scalar(softening_sq), self._params.ptr if table is not None else None, self.mode, stream),
-              "nb_ensemble_integrate")
+        self._call("integrate", self._pos[1 - self.current_read].ptr, self._pos[self.current_read].ptr, self._vel.ptr, self.num_bodies, self.num_systems,
+                   self._scalar(delta_time), self._scalar(damping), self._scalar(softening_sq), self._params.ptr if table is not None else None, self.mode, stream)
         self.current_read = 1 - self.current_read
 
-    def synchronize(self) -> None:
-        check(lib().nb_device_synchronize(), "nb_device_synchronize")
+    def _buffers(self):
+        return self._pos + [self._vel] + ([self._params] if self._params is not None else [])
 
     def free(self) -> None:
-        for b in self._pos + [self._vel] + ([self._params] if self._params is not None else []):
-            b.free()
+        super().free()
         self._params = None
 
 
 def hermite_plan(num_bodies: int, dtype=np.float32) -> HermitePlan:
     """nb_hermite_plan_*: the geometry of the acceleration + jerk kernel for `num_bodies` bodies"""
-    p = HermitePlan()
-    fn = hermite_lib().nb_hermite_plan_f32 if np.dtype(dtype) == np.float32 else hermite_lib().nb_hermite_plan_f64
-    check(fn(num_bodies, ctypes.byref(p)), "nb_hermite_plan")
-    return p
+    return _plan(hermite_lib, "hermite", HermitePlan, dtype, num_bodies)
 
 
 def hermite_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(hermite_lib().nb_hermite_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_hermite_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(hermite_lib, "hermite", dtype, num_bodies)
 
 
-class HermiteSystem:
+class HermiteSystem(_HermiteState):
     """One system of N bodies on the device, stepped by the 4th-order Hermite scheme of include/nbody_hip_hermite.h.
 
     Positions (stepped in place: the call allows new == old), velocities, accelerations and jerks of 4*N T, the workspace and the
@@ -985,85 +983,49 @@ class HermiteSystem:
     accelerations and jerks from the stored state (what starts a run); ``step(dt)`` takes one step; ``suggested_dt(eta)`` reads
     eta * min |a| / |jerk| of the stored derivatives back."""
 
+    _library, _prefix = staticmethod(hermite_lib), "nb_hermite_"
+    _query, _scratch_bytes = staticmethod(hermite_workspace_bytes), HERMITE_TIMESTEP_SCRATCH_BYTES
+    _arrays = ("_pos", "_vel", "_acc", "_jerk")  # 4*N T each, allocated in this order
+
     def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies = int(num_bodies)
-        t = self.dtype.type
-        self.softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else t(softening_sq)
-        self._workspace_bytes = hermite_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
+        self.softening_sq = self.dtype.type(self._softening_or_default(softening_sq))
+        self._workspace_bytes = self._query(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
         self.shape = (self.num_bodies, 4)
-        nbytes = 4 * self.num_bodies * self.dtype.itemsize
-        self._pos, self._vel, self._acc, self._jerk = (DeviceBuffer(nbytes) for _ in range(4))
+        for name in self._arrays:
+            setattr(self, name, DeviceBuffer(4 * self.num_bodies * self.dtype.itemsize))
         self._workspace = DeviceBuffer(self._workspace_bytes)
-        self._scratch = DeviceBuffer(HERMITE_TIMESTEP_SCRATCH_BYTES)
+        self._scratch = DeviceBuffer(self._scratch_bytes)
         self._dt = DeviceBuffer(8)
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
 
     def _buffers(self):
         return [self._pos, self._vel, self._acc, self._jerk, self._workspace, self._scratch, self._dt]
 
-    def set_state(self, positions, velocities) -> None:
-        for buf, data in ((self._pos, positions), (self._vel, velocities)):
-            data = np.ascontiguousarray(data, dtype=self.dtype)
-            if data.shape != self.shape:
-                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
-            buf.upload(data)
-
     def eval(self, stream=None) -> None:
-        fn = getattr(hermite_lib(), "nb_hermite_eval_" + self._suffix)
-        check(fn(self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self._scalar(self.softening_sq), stream), "nb_hermite_eval")
+        self._call("eval", self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self._scalar(self.softening_sq), stream)
 
     def step(self, delta_time, stream=None) -> None:
-        fn = getattr(hermite_lib(), "nb_hermite_step_" + self._suffix)
-        check(fn(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
-                 self._scalar(delta_time), self._scalar(self.softening_sq), stream), "nb_hermite_step")
+        self._call("step", self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
+                   self._scalar(delta_time), self._scalar(self.softening_sq), stream)
+
+    def _derivatives(self):
+        return self._acc.ptr, self._jerk.ptr
 
     def suggested_dt(self, eta, stream=None):
-        fn = getattr(hermite_lib(), "nb_hermite_timestep_" + self._suffix)
-        check(fn(self._acc.ptr, self._jerk.ptr, self.num_bodies, self._scalar(eta), self._dt.ptr, self._scratch.ptr, HERMITE_TIMESTEP_SCRATCH_BYTES, stream),
-              "nb_hermite_timestep")
+        self._call("timestep", *self._derivatives(), self.num_bodies, self._scalar(eta), self._dt.ptr, self._scratch.ptr, self._scratch_bytes, stream)
         out = np.empty(1, dtype=self.dtype)
         check(lib().nb_d2h(out.ctypes.data_as(_vp), self._dt.ptr, out.nbytes, stream), "nb_d2h")
         return out[0]
 
-    def _download(self, buf: DeviceBuffer) -> np.ndarray:
-        return buf.download(np.empty(self.shape, dtype=self.dtype))
-
-    def get_positions(self) -> np.ndarray:
-        return self._download(self._pos)
-
-    def get_velocities(self) -> np.ndarray:
-        return self._download(self._vel)
-
-    def get_accelerations(self) -> np.ndarray:
-        return self._download(self._acc)
-
-    def get_jerks(self) -> np.ndarray:
-        return self._download(self._jerk)
-
-    def synchronize(self) -> None:
-        check(lib().nb_device_synchronize(), "nb_device_synchronize")
-
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
-
 
 def hermite6_plan(num_bodies: int, dtype=np.float32) -> Hermite6Plan:
     """nb_hermite6_plan_*: the geometry of the acceleration + jerk + snap kernel for `num_bodies` bodies"""
-    p = Hermite6Plan()
-    fn = hermite6_lib().nb_hermite6_plan_f32 if np.dtype(dtype) == np.float32 else hermite6_lib().nb_hermite6_plan_f64
-    check(fn(num_bodies, ctypes.byref(p)), "nb_hermite6_plan")
-    return p
+    return _plan(hermite6_lib, "hermite6", Hermite6Plan, dtype, num_bodies)
 
 
 def hermite6_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(hermite6_lib().nb_hermite6_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_hermite6_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(hermite6_lib, "hermite6", dtype, num_bodies)
 
 
 class Hermite6System(HermiteSystem):
@@ -1073,43 +1035,23 @@ class Hermite6System(HermiteSystem):
     jerks and snaps from the stored state and zeroes the crackles (what starts a run); ``step(dt)`` takes one step;
     ``suggested_dt(eta)`` reads Aarseth's eta sqrt(min (|a||s| + |j|^2) / (|j||c| + |s|^2)) of the stored derivatives back."""
 
-    def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
-        self.num_bodies = int(num_bodies)
-        t = self.dtype.type
-        self.softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else t(softening_sq)
-        self._workspace_bytes = hermite6_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
-        self.shape = (self.num_bodies, 4)
-        nbytes = 4 * self.num_bodies * self.dtype.itemsize
-        self._pos, self._vel, self._acc, self._jerk, self._snap, self._crackle = (DeviceBuffer(nbytes) for _ in range(6))
-        self._workspace = DeviceBuffer(self._workspace_bytes)
-        self._scratch = DeviceBuffer(HERMITE6_TIMESTEP_SCRATCH_BYTES)
-        self._dt = DeviceBuffer(8)
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
+    _library, _prefix = staticmethod(hermite6_lib), "nb_hermite6_"
+    _query, _scratch_bytes = staticmethod(hermite6_workspace_bytes), HERMITE6_TIMESTEP_SCRATCH_BYTES
+    _arrays = HermiteSystem._arrays + ("_snap", "_crackle")
 
     def _buffers(self):
         return super()._buffers() + [self._snap, self._crackle]
 
     def eval(self, stream=None) -> None:
-        fn = getattr(hermite6_lib(), "nb_hermite6_init_" + self._suffix)
-        check(fn(self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._pos.ptr, self._vel.ptr, self._workspace.ptr, self._workspace_bytes,
-                 self.num_bodies, self._scalar(self.softening_sq), stream), "nb_hermite6_init")
+        self._call("init", self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._pos.ptr, self._vel.ptr, self._workspace.ptr, self._workspace_bytes,
+                   self.num_bodies, self._scalar(self.softening_sq), stream)
 
     def step(self, delta_time, stream=None) -> None:
-        fn = getattr(hermite6_lib(), "nb_hermite6_step_" + self._suffix)
-        check(fn(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._workspace.ptr,
-                 self._workspace_bytes, self.num_bodies, self._scalar(delta_time), self._scalar(self.softening_sq), stream), "nb_hermite6_step")
+        self._call("step", self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._workspace.ptr,
+                   self._workspace_bytes, self.num_bodies, self._scalar(delta_time), self._scalar(self.softening_sq), stream)
 
-    def suggested_dt(self, eta, stream=None):
-        fn = getattr(hermite6_lib(), "nb_hermite6_timestep_" + self._suffix)
-        check(fn(self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self.num_bodies, self._scalar(eta), self._dt.ptr, self._scratch.ptr,
-                 HERMITE6_TIMESTEP_SCRATCH_BYTES, stream), "nb_hermite6_timestep")
-        out = np.empty(1, dtype=self.dtype)
-        check(lib().nb_d2h(out.ctypes.data_as(_vp), self._dt.ptr, out.nbytes, stream), "nb_d2h")
-        return out[0]
+    def _derivatives(self):
+        return self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr
 
     def get_snaps(self) -> np.ndarray:
         return self._download(self._snap)
@@ -1120,20 +1062,14 @@ class Hermite6System(HermiteSystem):
 
 def hermite_ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> HermiteEnsemblePlan:
     """nb_hermite_ensemble_plan_*: the geometry of `num_systems` systems of `num_bodies` bodies"""
-    p = HermiteEnsemblePlan()
-    fn = getattr(hermite_ensemble_lib(), "nb_hermite_ensemble_plan_" + ("f32" if np.dtype(dtype) == np.float32 else "f64"))
-    check(fn(num_bodies, num_systems, ctypes.byref(p)), "nb_hermite_ensemble_plan")
-    return p
+    return _plan(hermite_ensemble_lib, "hermite_ensemble", HermiteEnsemblePlan, dtype, num_bodies, num_systems)
 
 
 def hermite_ensemble_workspace_bytes(num_bodies: int, num_systems: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(hermite_ensemble_lib().nb_hermite_ensemble_workspace_bytes(num_bodies, num_systems, np.dtype(dtype).itemsize, ctypes.byref(out)),
-          "nb_hermite_ensemble_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(hermite_ensemble_lib, "hermite_ensemble", dtype, num_bodies, num_systems)
 
 
-class HermiteEnsemble:
+class HermiteEnsemble(_HermiteState):
     """B independent systems of N bodies on the device, stepped together by the 4th-order Hermite scheme of
     include/nbody_hip_hermite_ensemble.h.
 
@@ -1144,12 +1080,11 @@ class HermiteEnsemble:
     ``begin(eta)``, then ``advance(t_stop, eta, dt_max, calls)`` enqueues `calls` calls without reading anything back; ``clocks()`` and
     ``status()`` read the device records.  `softening_sq`: a scalar or one value per system."""
 
+    _library, _prefix = staticmethod(hermite_ensemble_lib), "nb_hermite_ensemble_"
+
     def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, softening_sq=None):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies, self.num_systems = int(num_bodies), int(num_systems)
-        t = self.dtype.type
         self._workspace_bytes = hermite_ensemble_workspace_bytes(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
         self.shape = (self.num_systems, self.num_bodies, 4)
         nbytes = 4 * self.num_bodies * self.num_systems * self.dtype.itemsize
@@ -1160,39 +1095,14 @@ class HermiteEnsemble:
         self._per_system = DeviceBuffer(self.num_systems * self.dtype.itemsize)  # dt_out
         self._params = DeviceBuffer(4 * self.num_systems * self.dtype.itemsize)
         self._system_eps2 = None
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
-        softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else softening_sq
-        if np.ndim(softening_sq) == 0:
-            self.softening_sq = np.full(self.num_systems, softening_sq, self.dtype)
-        else:
-            self.softening_sq = np.ascontiguousarray(softening_sq, dtype=self.dtype)
-            if self.softening_sq.shape != (self.num_systems,):
-                self.free()
-                raise ValueError(f"softening_sq: a scalar or {self.num_systems} values")
-            self._system_eps2 = DeviceBuffer(self.softening_sq.nbytes)
-            self._system_eps2.upload(self.softening_sq)
+        self._set_system_softening(softening_sq)
 
     def _buffers(self):
         return [b for b in (self._pos, self._vel, self._acc, self._jerk, self._workspace, self._clocks, self._status, self._per_system, self._params, self._system_eps2)
                 if b is not None]
 
-    def _fn(self, name):
-        return getattr(hermite_ensemble_lib(), f"nb_hermite_ensemble_{name}_{self._suffix}")
-
-    def _softening(self):
-        return self._scalar(self.softening_sq[0]), (self._system_eps2.ptr if self._system_eps2 is not None else None)
-
-    def set_state(self, positions, velocities) -> None:
-        for buf, data in ((self._pos, positions), (self._vel, velocities)):
-            data = np.ascontiguousarray(data, dtype=self.dtype)
-            if data.shape != self.shape:
-                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
-            buf.upload(data)
-
     def eval(self, stream=None) -> None:
-        check(self._fn("eval")(self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self.num_systems, *self._softening(), stream),
-              "nb_hermite_ensemble_eval")
+        self._call("eval", self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self.num_systems, *self._softening(), stream)
 
     def step(self, delta_time, stream=None) -> None:
         """One step of every system: `delta_time` a scalar, or one dt per system (uploaded first, with the systems' softening^2)."""
@@ -1201,27 +1111,26 @@ class HermiteEnsemble:
             table = np.zeros((self.num_systems, 4), self.dtype)
             table[:, 0], table[:, 1] = delta_time, self.softening_sq
             self._params.upload(table)
-        check(self._fn("step")(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
-                               self.num_systems, self._scalar(0 if table is not None else delta_time), self._scalar(self.softening_sq[0]),
-                               self._params.ptr if table is not None else None, stream), "nb_hermite_ensemble_step")
+        self._call("step", self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
+                   self.num_systems, self._scalar(0 if table is not None else delta_time), self._scalar(self.softening_sq[0]),
+                   self._params.ptr if table is not None else None, stream)
 
     def suggested_dt(self, eta, stream=None) -> np.ndarray:
-        check(self._fn("timestep")(self._acc.ptr, self._jerk.ptr, self.num_bodies, self.num_systems, self._scalar(eta), self._per_system.ptr, self._workspace.ptr,
-                                   self._workspace_bytes, stream), "nb_hermite_ensemble_timestep")
+        self._call("timestep", self._acc.ptr, self._jerk.ptr, self.num_bodies, self.num_systems, self._scalar(eta), self._per_system.ptr, self._workspace.ptr,
+                   self._workspace_bytes, stream)
         out = np.empty(self.num_systems, dtype=self.dtype)
         check(lib().nb_d2h(out.ctypes.data_as(_vp), self._per_system.ptr, out.nbytes, stream), "nb_d2h")
         return out
 
     def begin(self, eta, stream=None) -> None:
-        check(self._fn("begin")(self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self._clocks.ptr, self.num_bodies, self.num_systems, *self._softening(),
-                                self._scalar(eta), self._workspace.ptr, self._workspace_bytes, stream), "nb_hermite_ensemble_begin")
+        self._call("begin", self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self._clocks.ptr, self.num_bodies, self.num_systems, *self._softening(),
+                   self._scalar(eta), self._workspace.ptr, self._workspace_bytes, stream)
 
     def advance(self, t_stop, eta, dt_max=float("inf"), calls: int = 1, stream=None) -> None:
         """`calls` calls of nb_hermite_ensemble_advance_*: every system that can still move takes `calls` steps towards t_stop; nothing is read back."""
         for _ in range(calls):
-            check(self._fn("advance")(self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._clocks.ptr, self._status.ptr, self._workspace.ptr,
-                                      self._workspace_bytes, self.num_bodies, self.num_systems, float(t_stop), float(dt_max), self._scalar(eta), *self._softening(), stream),
-                  "nb_hermite_ensemble_advance")
+            self._call("advance", self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._clocks.ptr, self._status.ptr, self._workspace.ptr,
+                       self._workspace_bytes, self.num_bodies, self.num_systems, float(t_stop), float(dt_max), self._scalar(eta), *self._softening(), stream)
 
     def clocks(self) -> np.ndarray:
         """the systems' clocks as a structured array (HERMITE_ENSEMBLE_CLOCK_DTYPE)"""
@@ -1232,44 +1141,17 @@ class HermiteEnsemble:
         raw = self._status.download(np.empty(ctypes.sizeof(HermiteEnsembleStatus), dtype=np.uint8))
         return HermiteEnsembleStatus.from_buffer_copy(raw.tobytes())
 
-    def _download(self, buf: DeviceBuffer) -> np.ndarray:
-        return buf.download(np.empty(self.shape, dtype=self.dtype))
-
-    def get_positions(self) -> np.ndarray:
-        return self._download(self._pos)
-
-    def get_velocities(self) -> np.ndarray:
-        return self._download(self._vel)
-
-    def get_accelerations(self) -> np.ndarray:
-        return self._download(self._acc)
-
-    def get_jerks(self) -> np.ndarray:
-        return self._download(self._jerk)
-
-    def synchronize(self) -> None:
-        check(lib().nb_device_synchronize(), "nb_device_synchronize")
-
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
-
 
 def hermite_block_plan(num_bodies: int, num_active: int, dtype=np.float32) -> HermiteBlockPlan:
     """nb_hermite_block_plan_*: the geometry of a block step of `num_active` of `num_bodies` bodies"""
-    p = HermiteBlockPlan()
-    fn = hermite_block_lib().nb_hermite_block_plan_f32 if np.dtype(dtype) == np.float32 else hermite_block_lib().nb_hermite_block_plan_f64
-    check(fn(num_bodies, num_active, ctypes.byref(p)), "nb_hermite_block_plan")
-    return p
+    return _plan(hermite_block_lib, "hermite_block", HermiteBlockPlan, dtype, num_bodies, num_active)
 
 
 def hermite_block_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(hermite_block_lib().nb_hermite_block_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_hermite_block_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(hermite_block_lib, "hermite_block", dtype, num_bodies)
 
 
-class HermiteBlockSystem:
+class HermiteBlockSystem(_HermiteState):
     """One system of N bodies on the device, stepped by the Hermite scheme with block time steps of include/nbody_hip_hermite_block.h.
 
     The state (positions, velocities, accelerations, jerks, ticks, levels), the status record and the workspace are owned here.
@@ -1277,13 +1159,12 @@ class HermiteBlockSystem:
     enqueues one block step; ``advance(t_stop, batch)`` enqueues batches of block steps and reads the status between them until a
     step would pass t_stop; ``snapshot()`` is the synchronised state at the status time; ``status()`` the status record."""
 
+    _library, _prefix = staticmethod(hermite_block_lib), "nb_hermite_block_"
+
     def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None, eta=0.02, eta_start=0.01, dt_max=0.125, max_level=30):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies = int(num_bodies)
-        t = self.dtype.type
-        self.softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else t(softening_sq)
+        self.softening_sq = self.dtype.type(self._softening_or_default(softening_sq))
         self.params = HermiteBlockParams(float(eta), float(eta_start), float(dt_max), int(max_level), 0)
         self.tick = float(dt_max) * 2.0 ** -int(max_level)
         self._workspace_bytes = hermite_block_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
@@ -1293,8 +1174,6 @@ class HermiteBlockSystem:
         self._ticks, self._levels = DeviceBuffer(8 * self.num_bodies), DeviceBuffer(4 * self.num_bodies)
         self._status = DeviceBuffer(ctypes.sizeof(HermiteBlockStatus))
         self._workspace = DeviceBuffer(self._workspace_bytes)
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
 
     def _buffers(self):
         return [self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out, self._ticks, self._levels, self._status, self._workspace]
@@ -1303,20 +1182,11 @@ class HermiteBlockSystem:
         return (self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._levels.ptr, self._status.ptr, self._workspace.ptr,
                 self._workspace_bytes, self.num_bodies, self._scalar(self.softening_sq), ctypes.byref(self.params))
 
-    def set_state(self, positions, velocities) -> None:
-        for buf, data in ((self._pos, positions), (self._vel, velocities)):
-            data = np.ascontiguousarray(data, dtype=self.dtype)
-            if data.shape != self.shape:
-                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
-            buf.upload(data)
-
     def init(self, stream=None) -> None:
-        fn = getattr(hermite_block_lib(), "nb_hermite_block_init_" + self._suffix)
-        check(fn(*self._state_args(), stream), "nb_hermite_block_init")
+        self._call("init", *self._state_args(), stream)
 
     def step(self, t_stop=float("inf"), stream=None) -> None:
-        fn = getattr(hermite_block_lib(), "nb_hermite_block_step_" + self._suffix)
-        check(fn(*self._state_args(), float(t_stop), stream), "nb_hermite_block_step")
+        self._call("step", *self._state_args(), float(t_stop), stream)
 
     def status(self, stream=None) -> HermiteBlockStatus:
         out = HermiteBlockStatus()
@@ -1343,27 +1213,11 @@ class HermiteBlockSystem:
 
     def sync(self, stream=None) -> None:
         """the synchronised snapshot, left on the device: snapshot_ptrs() for nb_energy_*"""
-        fn = getattr(hermite_block_lib(), "nb_hermite_block_sync_" + self._suffix)
-        check(fn(self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._status.ptr,
-                 self.num_bodies, ctypes.byref(self.params), stream), "nb_hermite_block_sync")
+        self._call("sync", self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._status.ptr,
+                   self.num_bodies, ctypes.byref(self.params), stream)
 
     def snapshot_ptrs(self):
         return self._pos_out.ptr, self._vel_out.ptr
-
-    def _download(self, buf: DeviceBuffer) -> np.ndarray:
-        return buf.download(np.empty(self.shape, dtype=self.dtype))
-
-    def get_positions(self) -> np.ndarray:
-        return self._download(self._pos)
-
-    def get_velocities(self) -> np.ndarray:
-        return self._download(self._vel)
-
-    def get_accelerations(self) -> np.ndarray:
-        return self._download(self._acc)
-
-    def get_jerks(self) -> np.ndarray:
-        return self._download(self._jerk)
 
     def get_ticks(self) -> np.ndarray:
         return self._ticks.download(np.empty(self.num_bodies, dtype=np.uint64))
@@ -1371,30 +1225,17 @@ class HermiteBlockSystem:
     def get_levels(self) -> np.ndarray:
         return self._levels.download(np.empty(self.num_bodies, dtype=np.int32))
 
-    def synchronize(self) -> None:
-        check(lib().nb_device_synchronize(), "nb_device_synchronize")
-
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
-
 
 def hermite_block_ensemble_plan(num_bodies: int, num_systems: int, num_active: int, dtype=np.float32) -> HermiteBlockEnsemblePlan:
     """nb_hermite_block_ensemble_plan_*: the solo geometry of a block step of `num_active` of `num_bodies` bodies, and the grids of `num_systems` systems"""
-    p = HermiteBlockEnsemblePlan()
-    fn = getattr(hermite_block_ensemble_lib(), "nb_hermite_block_ensemble_plan_" + ("f32" if np.dtype(dtype) == np.float32 else "f64"))
-    check(fn(num_bodies, num_systems, num_active, ctypes.byref(p)), "nb_hermite_block_ensemble_plan")
-    return p
+    return _plan(hermite_block_ensemble_lib, "hermite_block_ensemble", HermiteBlockEnsemblePlan, dtype, num_bodies, num_systems, num_active)
 
 
 def hermite_block_ensemble_workspace_bytes(num_bodies: int, num_systems: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(hermite_block_ensemble_lib().nb_hermite_block_ensemble_workspace_bytes(num_bodies, num_systems, np.dtype(dtype).itemsize, ctypes.byref(out)),
-          "nb_hermite_block_ensemble_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(hermite_block_ensemble_lib, "hermite_block_ensemble", dtype, num_bodies, num_systems)
 
 
-class HermiteBlockEnsemble:
+class HermiteBlockEnsemble(_HermiteState):
     """B independent systems of N bodies on the device, each stepped by the Hermite scheme with block time steps of
     include/nbody_hip_hermite_block.h, all of them in the launches of one call (include/nbody_hip_hermite_block_ensemble.h).
 
@@ -1406,12 +1247,11 @@ class HermiteBlockEnsemble:
     own status time.  `params`: a HermiteBlockParams (default: eta 0.02, eta_start 0.01, dt_max 0.125, 30 levels); `softening_sq`: a
     scalar or one value per system."""
 
+    _library, _prefix = staticmethod(hermite_block_ensemble_lib), "nb_hermite_block_ensemble_"
+
     def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, params=None, softening_sq=None):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies, self.num_systems = int(num_bodies), int(num_systems)
-        t = self.dtype.type
         self.params = HermiteBlockParams(0.02, 0.01, 0.125, 30, 0) if params is None else params
         self.tick = float(self.params.dt_max) * 2.0 ** -int(self.params.max_level)
         self._workspace_bytes = hermite_block_ensemble_workspace_bytes(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
@@ -1424,43 +1264,21 @@ class HermiteBlockEnsemble:
         self._status = DeviceBuffer(ctypes.sizeof(HermiteBlockStatus) * self.num_systems)
         self._summary = DeviceBuffer(ctypes.sizeof(HermiteBlockEnsembleSummary))
         self._workspace = DeviceBuffer(self._workspace_bytes)
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
-        softening_sq = t(np.float32(0.1)) * t(np.float32(0.1)) if softening_sq is None else softening_sq
-        if np.ndim(softening_sq) == 0:
-            self.softening_sq = np.full(self.num_systems, softening_sq, self.dtype)
-        else:
-            self.softening_sq = np.ascontiguousarray(softening_sq, dtype=self.dtype)
-            if self.softening_sq.shape != (self.num_systems,):
-                self.free()
-                raise ValueError(f"softening_sq: a scalar or {self.num_systems} values")
-            self._system_eps2 = DeviceBuffer(self.softening_sq.nbytes)
-            self._system_eps2.upload(self.softening_sq)
+        self._set_system_softening(softening_sq)
 
     def _buffers(self):
         return [b for b in (self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out, self._ticks, self._levels, self._status, self._summary,
                             self._workspace, self._system_eps2) if b is not None]
 
-    def _fn(self, name):
-        return getattr(hermite_block_ensemble_lib(), f"nb_hermite_block_ensemble_{name}_{self._suffix}")
-
     def _state_args(self):
         return (self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._levels.ptr, self._status.ptr, self._workspace.ptr,
-                self._workspace_bytes, self.num_bodies, self.num_systems, self._scalar(self.softening_sq[0]),
-                self._system_eps2.ptr if self._system_eps2 is not None else None, ctypes.byref(self.params))
-
-    def set_state(self, positions, velocities) -> None:
-        for buf, data in ((self._pos, positions), (self._vel, velocities)):
-            data = np.ascontiguousarray(data, dtype=self.dtype)
-            if data.shape != self.shape:
-                raise ValueError(f"expected an array of shape {self.shape}, got {data.shape}")
-            buf.upload(data)
+                self._workspace_bytes, self.num_bodies, self.num_systems, *self._softening(), ctypes.byref(self.params))
 
     def init(self, stream=None) -> None:
-        check(self._fn("init")(*self._state_args(), stream), "nb_hermite_block_ensemble_init")
+        self._call("init", *self._state_args(), stream)
 
     def step(self, t_stop=float("inf"), stream=None) -> None:
-        check(self._fn("step")(*self._state_args(), float(t_stop), stream), "nb_hermite_block_ensemble_step")
+        self._call("step", *self._state_args(), float(t_stop), stream)
 
     def summary(self, stream=None) -> HermiteBlockEnsembleSummary:
         """the status records folded on the device (one launch), then 64 bytes read"""
@@ -1489,8 +1307,8 @@ class HermiteBlockEnsemble:
 
     def sync(self, stream=None) -> None:
         """the synchronised snapshots, left on the device: snapshot_ptrs() for nb_energy_* (system s at byte offset s * 4 N sizeof T)"""
-        check(self._fn("sync")(self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._status.ptr,
-                               self.num_bodies, self.num_systems, ctypes.byref(self.params), stream), "nb_hermite_block_ensemble_sync")
+        self._call("sync", self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._ticks.ptr, self._status.ptr,
+                   self.num_bodies, self.num_systems, ctypes.byref(self.params), stream)
 
     def snapshot(self, stream=None):
         """(positions, velocities) of every body predicted to its system's status time (nb_hermite_block_ensemble_sync_*)"""
@@ -1501,54 +1319,27 @@ class HermiteBlockEnsemble:
     def snapshot_ptrs(self):
         return self._pos_out.ptr, self._vel_out.ptr
 
-    def _download(self, buf: DeviceBuffer) -> np.ndarray:
-        return buf.download(np.empty(self.shape, dtype=self.dtype))
-
-    def get_positions(self) -> np.ndarray:
-        return self._download(self._pos)
-
-    def get_velocities(self) -> np.ndarray:
-        return self._download(self._vel)
-
-    def get_accelerations(self) -> np.ndarray:
-        return self._download(self._acc)
-
-    def get_jerks(self) -> np.ndarray:
-        return self._download(self._jerk)
-
     def get_ticks(self) -> np.ndarray:
         return self._ticks.download(np.empty(self.shape[:2], dtype=np.uint64))
 
     def get_levels(self) -> np.ndarray:
         return self._levels.download(np.empty(self.shape[:2], dtype=np.int32))
 
-    def synchronize(self) -> None:
-        check(lib().nb_device_synchronize(), "nb_device_synchronize")
-
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
-
 
 def neighbour_plan(num_bodies: int, dtype=np.float32) -> NeighbourPlan:
     """nb_neighbour_plan_*: the geometry of a survey and of the lists of `num_bodies` bodies"""
-    p = NeighbourPlan()
-    fn = neighbour_lib().nb_neighbour_plan_f32 if np.dtype(dtype) == np.float32 else neighbour_lib().nb_neighbour_plan_f64
-    check(fn(num_bodies, ctypes.byref(p)), "nb_neighbour_plan")
-    return p
+    return _plan(neighbour_lib, "neighbour", NeighbourPlan, dtype, num_bodies)
 
 
 def neighbour_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(neighbour_lib().nb_neighbour_workspace_bytes(num_bodies, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_neighbour_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(neighbour_lib, "neighbour", dtype, num_bodies)
 
 
 def neighbour_status_dict(status: NeighbourStatus) -> dict:
     return {name: getattr(status, name) for name, _ in NeighbourStatus._fields_ if name != "reserved"}
 
 
-class NeighbourSurvey:
+class NeighbourSurvey(_DeviceState):
     """Nearest neighbours, counts, potentials and neighbour lists of states of N bodies (include/nbody_hip_neighbour.h).
 
     The outputs, the status record, the workspace and a staging copy of the positions are device buffers owned here.  ``positions`` is
@@ -1556,10 +1347,10 @@ class NeighbourSurvey:
     ``radii_sq`` likewise (T[N]).  ``survey`` and ``lists`` enqueue on `stream`, wait for it and return numpy arrays plus the status
     record as a dict; ``enqueue_survey`` / ``enqueue_lists`` only enqueue (outputs stay on the device: see the ``*_ptr`` attributes)."""
 
+    _library, _prefix = staticmethod(neighbour_lib), "nb_neighbour_"
+
     def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=0.0):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies = n = int(num_bodies)
         self.softening_sq = self.dtype.type(softening_sq)
         self._workspace_bytes = neighbour_workspace_bytes(n, self.dtype)  # refuses the sizes the calls refuse
@@ -1571,24 +1362,10 @@ class NeighbourSurvey:
         self._indices = None
         self._status = DeviceBuffer(ctypes.sizeof(NeighbourStatus))
         self._workspace = DeviceBuffer(self._workspace_bytes)
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
 
     def _buffers(self):
         return [b for b in (self._pos, self._radii, self._nearest, self._counts, self._nearest_d2, self._potentials, self._offsets, self._indices, self._status,
                             self._workspace) if b is not None]
-
-    def _device(self, data, own: DeviceBuffer, shape):
-        """the device address of `data`: its own when it is one, else a host array uploaded into `own`"""
-        if isinstance(data, DeviceBuffer):
-            return data.ptr
-        if isinstance(data, (int, ctypes.c_void_p)):
-            return data
-        host = np.ascontiguousarray(data, dtype=self.dtype)
-        if host.shape != shape:
-            raise ValueError(f"expected an array of shape {shape}, got {host.shape}")
-        own.upload(host)
-        return own.ptr
 
     def _radius(self, radius_sq, radii_sq):
         if (radius_sq is None) == (radii_sq is None):
@@ -1599,10 +1376,9 @@ class NeighbourSurvey:
 
     def enqueue_survey(self, positions, radius_sq=None, radii_sq=None, potentials=False, stream=None) -> None:
         radius, radii = self._radius(radius_sq, radii_sq)
-        fn = getattr(neighbour_lib(), "nb_neighbour_survey_" + self._suffix)
-        check(fn(self._device(positions, self._pos, (self.num_bodies, 4)), self.num_bodies, radius, radii, self._scalar(self.softening_sq), self._nearest.ptr,
-                 self._nearest_d2.ptr, self._counts.ptr, self._potentials.ptr if potentials else None, self._status.ptr, self._workspace.ptr,
-                 self._workspace_bytes, stream), "nb_neighbour_survey")
+        self._call("survey", self._device(positions, self._pos, (self.num_bodies, 4)), self.num_bodies, radius, radii, self._scalar(self.softening_sq), self._nearest.ptr,
+                   self._nearest_d2.ptr, self._counts.ptr, self._potentials.ptr if potentials else None, self._status.ptr, self._workspace.ptr,
+                   self._workspace_bytes, stream)
 
     def enqueue_lists(self, positions, radius_sq=None, radii_sq=None, capacity: int = 0, stream=None) -> None:
         radius, radii = self._radius(radius_sq, radii_sq)
@@ -1611,9 +1387,8 @@ class NeighbourSurvey:
             if self._indices is not None:
                 self._indices.free()
             self._indices = DeviceBuffer(4 * capacity)
-        fn = getattr(neighbour_lib(), "nb_neighbour_lists_" + self._suffix)
-        check(fn(self._device(positions, self._pos, (self.num_bodies, 4)), self.num_bodies, radius, radii, self._offsets.ptr,
-                 self._indices.ptr if capacity > 0 else None, capacity, self._status.ptr, self._workspace.ptr, self._workspace_bytes, stream), "nb_neighbour_lists")
+        self._call("lists", self._device(positions, self._pos, (self.num_bodies, 4)), self.num_bodies, radius, radii, self._offsets.ptr,
+                   self._indices.ptr if capacity > 0 else None, capacity, self._status.ptr, self._workspace.ptr, self._workspace_bytes, stream)
 
     def status(self, stream=None) -> dict:
         out = NeighbourStatus()
@@ -1663,23 +1438,14 @@ class NeighbourSurvey:
     def status_ptr(self):
         return self._status.ptr
 
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
-
 
 def knn_plan(num_bodies: int, k: int, dtype=np.float32) -> KnnPlan:
     """nb_knn_plan_*: the geometry of a survey of the `k` nearest neighbours of `num_bodies` bodies"""
-    p = KnnPlan()
-    fn = knn_lib().nb_knn_plan_f32 if np.dtype(dtype) == np.float32 else knn_lib().nb_knn_plan_f64
-    check(fn(num_bodies, k, ctypes.byref(p)), "nb_knn_plan")
-    return p
+    return _plan(knn_lib, "knn", KnnPlan, dtype, num_bodies, k)
 
 
 def knn_workspace_bytes(num_bodies: int, k: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(knn_lib().nb_knn_workspace_bytes(num_bodies, k, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_knn_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(knn_lib, "knn", dtype, num_bodies, k)
 
 
 def knn_structure_dict(record: KnnStructure) -> dict:
@@ -1688,7 +1454,7 @@ def knn_structure_dict(record: KnnStructure) -> dict:
     return out
 
 
-class KnnSurvey:
+class KnnSurvey(_DeviceState):
     """The K nearest neighbours of every body, local densities and the structure record of states of N bodies (include/nbody_hip_knn.h).
 
     The outputs, the record, the workspace and a staging copy of the positions are device buffers owned here, sized for `max_k`.
@@ -1696,10 +1462,10 @@ class KnnSurvey:
     {x, y, z, m}.  ``survey`` enqueues on `stream`, waits for it and returns numpy arrays plus the record as a dict; ``enqueue_survey``
     only enqueues (outputs stay on the device: see the ``*_ptr`` attributes)."""
 
+    _library, _prefix = staticmethod(knn_lib), "nb_knn_"
+
     def __init__(self, num_bodies: int, dtype=np.float32, max_k: int = KNN_MAX_K):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_bodies = n = int(num_bodies)
         self.max_k = int(max_k)
         self._workspace_bytes = knn_workspace_bytes(n, self.max_k, self.dtype)  # refuses the sizes the calls refuse; the same for every K
@@ -1709,7 +1475,6 @@ class KnnSurvey:
         self._densities = DeviceBuffer(n * size)
         self._structure = DeviceBuffer(ctypes.sizeof(KnnStructure))
         self._workspace = DeviceBuffer(self._workspace_bytes)
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
         self._positions = None  # what the last survey looked at: a host copy, or the device address
         self._centre = None  # the density centre of the last survey with the record
 
@@ -1723,19 +1488,10 @@ class KnnSurvey:
             raise ValueError(f"k must be in 1 .. {self.max_k}")
         densities = k >= 2 if densities is None else bool(densities)
         structure = k >= 2 if structure is None else bool(structure)
-        if isinstance(positions, DeviceBuffer):
-            address = self._positions = positions.ptr
-        elif isinstance(positions, (int, ctypes.c_void_p)):
-            address = self._positions = positions
-        else:
-            host = np.ascontiguousarray(positions, dtype=self.dtype)
-            if host.shape != (self.num_bodies, 4):
-                raise ValueError(f"expected an array of shape {(self.num_bodies, 4)}, got {host.shape}")
-            self._pos.upload(host)
-            address, self._positions = self._pos.ptr, host.copy()
-        fn = getattr(knn_lib(), "nb_knn_survey_" + self._suffix)
-        check(fn(address, self.num_bodies, k, self._index.ptr, self._dist_sq.ptr, self._densities.ptr if densities else None,
-                 self._structure.ptr if structure else None, self._workspace.ptr, self._workspace_bytes, stream), "nb_knn_survey")
+        address = self._device(positions, self._pos, (self.num_bodies, 4))
+        self._positions = address if isinstance(positions, (DeviceBuffer, int, ctypes.c_void_p)) else np.array(positions, dtype=self.dtype)
+        self._call("survey", address, self.num_bodies, k, self._index.ptr, self._dist_sq.ptr, self._densities.ptr if densities else None,
+                   self._structure.ptr if structure else None, self._workspace.ptr, self._workspace_bytes, stream)
 
     def structure(self, stream=None) -> dict:
         out = KnnStructure()
@@ -1785,10 +1541,6 @@ class KnnSurvey:
     def structure_ptr(self):
         return self._structure.ptr
 
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
-
 
 def lagrangian_radii(positions, centre, fractions) -> np.ndarray:
     """positions (N, 4) {x, y, z, m}: for each fraction f the smallest distance from `centre` whose bodies (all within it, in float64) hold
@@ -1803,19 +1555,14 @@ def lagrangian_radii(positions, centre, fractions) -> np.ndarray:
 
 def field_plan(num_sources: int, num_targets: int, dtype=np.float32) -> FieldPlan:
     """nb_field_plan_*: the geometry of an evaluation of `num_sources` sources at `num_targets` points"""
-    p = FieldPlan()
-    fn = field_lib().nb_field_plan_f32 if np.dtype(dtype) == np.float32 else field_lib().nb_field_plan_f64
-    check(fn(num_sources, num_targets, ctypes.byref(p)), "nb_field_plan")
-    return p
+    return _plan(field_lib, "field", FieldPlan, dtype, num_sources, num_targets)
 
 
 def field_workspace_bytes(num_sources: int, num_targets: int, dtype=np.float32) -> int:
-    out = _sz(0)
-    check(field_lib().nb_field_workspace_bytes(num_sources, num_targets, np.dtype(dtype).itemsize, ctypes.byref(out)), "nb_field_workspace_bytes")
-    return out.value
+    return _query_workspace_bytes(field_lib, "field", dtype, num_sources, num_targets)
 
 
-class FieldProbe:
+class FieldProbe(_DeviceState):
     """Acceleration, jerk and potential of N sources at up to `max_targets` points of the caller's own (include/nbody_hip_field.h).
 
     The outputs, the workspace (sized for every M up to `max_targets`) and staging copies of the inputs are device buffers owned here.
@@ -1824,10 +1571,10 @@ class FieldProbe:
     ``targets`` needs ``num_targets``.  ``eval`` enqueues on `stream`, waits for it and returns numpy arrays; ``enqueue`` only enqueues
     (outputs stay on the device: see the ``*_ptr`` attributes)."""
 
+    _library, _prefix = staticmethod(field_lib), "nb_field_"
+
     def __init__(self, num_sources: int, max_targets: int, dtype=np.float32, softening_sq=0.0):
-        self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("float32 or float64")
+        super().__init__(dtype)
         self.num_sources, self.max_targets = n, m = int(num_sources), int(max_targets)
         self.softening_sq = self.dtype.type(softening_sq)
         size, per_tile = self.dtype.itemsize, 128 if self.dtype == np.float32 else 64
@@ -1840,25 +1587,13 @@ class FieldProbe:
         self._tgt, self._tgt_vel, self._self = DeviceBuffer(4 * m * size), DeviceBuffer(4 * m * size), DeviceBuffer(4 * m)
         self._acc, self._jerk, self._pot = DeviceBuffer(4 * m * size), DeviceBuffer(4 * m * size), DeviceBuffer(m * size)
         self._workspace = DeviceBuffer(max(self._workspace_bytes, 256))
-        self._scalar = np.float32 if self.dtype == np.float32 else float
-        self._suffix = "f32" if self.dtype == np.float32 else "f64"
 
     def _buffers(self):
         return [self._src, self._src_vel, self._tgt, self._tgt_vel, self._self, self._acc, self._jerk, self._pot, self._workspace]
 
     def _device(self, data, own: DeviceBuffer, shape, dtype=None):
-        """the device address of `data`: its own when it is one, else a host array uploaded into `own`"""
-        if data is None:
-            return None
-        if isinstance(data, DeviceBuffer):
-            return data.ptr
-        if isinstance(data, (int, ctypes.c_void_p)):
-            return data
-        host = np.ascontiguousarray(data, dtype=dtype or self.dtype)
-        if host.shape != shape:
-            raise ValueError(f"expected an array of shape {shape}, got {host.shape}")
-        own.upload(host)
-        return own.ptr
+        """... and None (an input left out) stays None"""
+        return None if data is None else super()._device(data, own, shape, dtype)
 
     def enqueue(self, sources, targets, source_velocities=None, target_velocities=None, self_index=None, num_targets=None, accelerations=True, jerks=False,
                 potentials=True, stream=None) -> int:
@@ -1873,11 +1608,10 @@ class FieldProbe:
         if jerks and (source_velocities is None or target_velocities is None):
             raise ValueError("jerks need source_velocities and target_velocities")
         n = self.num_sources
-        fn = getattr(field_lib(), "nb_field_eval_" + self._suffix)
-        check(fn(self._device(sources, self._src, (n, 4)), self._device(source_velocities, self._src_vel, (n, 4)), n, self._device(targets, self._tgt, (m, 4)),
-                 self._device(target_velocities, self._tgt_vel, (m, 4)), self._device(self_index, self._self, (m,), np.uint32), m, self._scalar(self.softening_sq),
-                 self._acc.ptr if accelerations else None, self._jerk.ptr if jerks else None, self._pot.ptr if potentials else None, self._workspace.ptr,
-                 self._workspace.nbytes, stream), "nb_field_eval")
+        self._call("eval", self._device(sources, self._src, (n, 4)), self._device(source_velocities, self._src_vel, (n, 4)), n, self._device(targets, self._tgt, (m, 4)),
+                   self._device(target_velocities, self._tgt_vel, (m, 4)), self._device(self_index, self._self, (m,), np.uint32), m, self._scalar(self.softening_sq),
+                   self._acc.ptr if accelerations else None, self._jerk.ptr if jerks else None, self._pot.ptr if potentials else None, self._workspace.ptr,
+                   self._workspace.nbytes, stream)
         return m
 
     def eval(self, sources, targets, source_velocities=None, target_velocities=None, self_index=None, jerks=False, potentials=True, stream=None, num_targets=None) -> dict:
@@ -1904,10 +1638,6 @@ class FieldProbe:
     @property
     def workspace_ptr(self):
         return self._workspace.ptr
-
-    def free(self) -> None:
-        for b in self._buffers():
-            b.free()
 
 
 class Event:

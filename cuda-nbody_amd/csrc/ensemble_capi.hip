@@ -1,9 +1,8 @@
 // ensemble_capi.hip -- the extern "C" boundary of libnbody_hip_ensemble.so (include/nbody_hip_ensemble.h).  Every argument is
 // checked on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_ensemble.h"
+#include "capi_check.h"
 #include "ensemble_kernels.h"
-
-#include <cstdint>
 
 namespace {
 
@@ -25,20 +24,10 @@ template <typename T> int plan_query(unsigned n, unsigned b, nb_ensemble_plan_t*
 
 template <typename T>
 int integrate(T* new_pos, const T* old_pos, T* vel, unsigned n, unsigned b, T dt, T damping, T eps2, const T* params, int mode, nb_stream_t stream) {
-    if (!new_pos || !old_pos || !vel || !sizes_ok(n, b)) return NB_ERR_INVALID_ARGUMENT;
+    if (!sizes_ok(n, b)) return NB_ERR_INVALID_ARGUMENT;
     if (mode != NB_MODE_STRICT && mode != NB_MODE_FAST) return NB_ERR_INVALID_ARGUMENT;
-    const auto addr    = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    const auto aligned = [&](const void* p) { return addr(p) % (4 * sizeof(T)) == 0; };
-    if (!aligned(new_pos) || !aligned(old_pos) || !aligned(vel) || (params && !aligned(params))) return NB_ERR_INVALID_ARGUMENT;
-    const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * b * 4 * sizeof(T);
-    const auto overlap = [&](const void* x, std::uintptr_t x_len, const void* y, std::uintptr_t y_len) { return addr(x) < addr(y) + y_len && addr(y) < addr(x) + x_len; };
-    if (overlap(new_pos, bodies, old_pos, bodies) || overlap(new_pos, bodies, vel, bodies) || overlap(vel, bodies, old_pos, bodies)) return NB_ERR_INVALID_ARGUMENT;
-    if (params) {
-        const std::uintptr_t param_bytes = static_cast<std::uintptr_t>(b) * 4 * sizeof(T);
-        for (const void* body_array : {static_cast<const void*>(new_pos), static_cast<const void*>(old_pos), static_cast<const void*>(vel)}) {
-            if (overlap(params, param_bytes, body_array, bodies)) return NB_ERR_INVALID_ARGUMENT;
-        }
-    }
+    const std::uintptr_t al = 4 * sizeof(T), bodies = static_cast<std::uintptr_t>(n) * b * al;
+    if (!nb::spans_ok({{new_pos, bodies, al}, {old_pos, bodies, al}, {vel, bodies, al}, {params, b * al, al, nb::Span::optional}})) return NB_ERR_INVALID_ARGUMENT;
     nb::EnsembleArgs<T> a{};
     a.new_pos = new_pos, a.old_pos = old_pos, a.vel = vel, a.params = params;
     a.n = n, a.dt = dt, a.damping = damping, a.eps2 = eps2;

@@ -1,32 +1,19 @@
 // field_capi.hip -- the extern "C" boundary of libnbody_hip_field.so (include/nbody_hip_field.h).  Every argument is checked on the
 // host before the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_field.h"
+#include "capi_check.h"
 #include "field_kernels.h"
-
-#include <cstdint>
+#include "softening_floor.h"
 
 namespace {
+
+using nb::floored, nb::Span, nb::spans_ok;
 
 static_assert(NB_FIELD_MAX_SOURCES == nb::kFieldMaxSources, "the header's limit is the kernels'");
 static_assert(NB_FIELD_MAX_TARGETS == nb::kFieldMaxTargets, "the header's limit is the kernels'");
 static_assert(NB_FIELD_NONE == nb::kFieldNone, "the header's `none` is the kernels'");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 bool sizes_ok(unsigned n, unsigned m) { return n >= 1 && n <= nb::kFieldMaxSources && m >= 1 && m <= nb::kFieldMaxTargets; }
-
-std::uintptr_t addr(const void* p) { return reinterpret_cast<std::uintptr_t>(p); }
-bool           aligned(const Span& s) { return s.p == nullptr || addr(s.p) % s.align == 0; }
-bool           overlap(const Span& x, const Span& y) {
-    return x.p != nullptr && y.p != nullptr && x.bytes > 0 && y.bytes > 0 && addr(x.p) < addr(y.p) + y.bytes && addr(y.p) < addr(x.p) + x.bytes;
-}
-
-// softening^2 == 0: the floor of nbody_hip_hermite.h
-template <typename T> T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
 
 template <typename T> int plan_query(unsigned n, unsigned m, nb_field_plan_t* out) {
     if (out == nullptr || !sizes_ok(n, m)) return NB_ERR_INVALID_ARGUMENT;
@@ -57,19 +44,10 @@ int eval(const T* src, const T* src_vel, unsigned n, const T* tgt, const T* tgt_
     const nb::FieldLayout l = nb::field_layout(n, m, sizeof(T));
     if (workspace_bytes < l.bytes || (l.bytes > 0 && workspace == nullptr)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t N = n, M = m, V = 4 * sizeof(T);
-    const Span           in[]  = {{src, N * V, V}, {src_vel, N * V, V}, {tgt, M * V, V}, {tgt_vel, M * V, V}, {self, M * 4, 4}};
-    const Span           out[] = {{acc, M * V, V}, {jerk, M * V, V}, {pot, M * sizeof(T), sizeof(T)}, {workspace, l.bytes, 32}};
-    for (const Span& s : in) {
-        if (!aligned(s)) return NB_ERR_INVALID_ARGUMENT;
-    }
-    for (int x = 0; x < 4; ++x) {
-        if (!aligned(out[x])) return NB_ERR_INVALID_ARGUMENT;
-        for (const Span& s : in) {
-            if (overlap(out[x], s)) return NB_ERR_INVALID_ARGUMENT;
-        }
-        for (int y = x + 1; y < 4; ++y) {
-            if (overlap(out[x], out[y])) return NB_ERR_INVALID_ARGUMENT;
-        }
+    // what the call writes, apart from each other and from what it reads; the inputs may alias each other
+    if (!spans_ok({{acc, M * V, V, Span::optional}, {jerk, M * V, V, Span::optional}, {pot, M * sizeof(T), sizeof(T), Span::optional}, {workspace, l.bytes, 32, Span::optional}},
+                  {{src, N * V, V}, {src_vel, N * V, V, Span::optional}, {tgt, M * V, V}, {tgt_vel, M * V, V, Span::optional}, {self, M * 4, 4, Span::optional}})) {
+        return NB_ERR_INVALID_ARGUMENT;
     }
     nb::FieldArgs<T> a{};
     a.src = src, a.src_vel = src_vel, a.tgt = tgt, a.tgt_vel = tgt_vel, a.self = self;
@@ -84,7 +62,7 @@ int eval(const T* src, const T* src_vel, unsigned n, const T* tgt, const T* tgt_
 extern "C" {
 
 int nb_field_workspace_bytes(unsigned num_sources, unsigned num_targets, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !sizes_ok(num_sources, num_targets) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !sizes_ok(num_sources, num_targets) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     *bytes = nb::field_layout(num_sources, num_targets, sizeof_T).bytes;
     return 0;
 }

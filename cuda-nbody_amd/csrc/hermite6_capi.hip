@@ -1,40 +1,18 @@
 // hermite6_capi.hip -- the extern "C" boundary of libnbody_hip_hermite6.so (include/nbody_hip_hermite6.h).  Every argument is checked
 // on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_hermite6.h"
+#include "capi_check.h"
 #include "hermite6_kernels.h"
-
-#include <cstdint>
-#include <initializer_list>
+#include "softening_floor.h"
 
 namespace {
+
+using nb::floored, nb::in_place_or_apart, nb::Span, nb::spans_ok;
 
 static_assert(NB_HERMITE6_MAX_BODIES == nb::kHermite6MaxBodies, "the header's limit is the kernels'");
 static_assert(NB_HERMITE6_TIMESTEP_SCRATCH_BYTES == nb::kHermite6TimestepPartials * sizeof(double), "the header's scratch size is the kernels'");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 bool size_ok(unsigned n) { return n >= 1 && n <= nb::kHermite6MaxBodies; }
-
-// no null, every span aligned, no two spans overlapping
-bool spans_ok(std::initializer_list<Span> spans) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (const Span& s : spans) {
-        if (s.p == nullptr || addr(s.p) % s.align != 0) return false;
-    }
-    for (const Span* x = spans.begin(); x != spans.end(); ++x) {
-        for (const Span* y = x + 1; y != spans.end(); ++y) {
-            if (addr(x->p) < addr(y->p) + y->bytes && addr(y->p) < addr(x->p) + x->bytes) return false;
-        }
-    }
-    return true;
-}
-
-// softening^2 == 0: the floor of the header (the i = j term contributes 0, not NaN)
-template <typename T> T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
 
 template <typename T> int plan_query(unsigned n, nb_hermite6_plan_t* out) {
     if (out == nullptr || !size_ok(n)) return NB_ERR_INVALID_ARGUMENT;
@@ -52,9 +30,9 @@ template <typename T> int eval(T* acc, T* jerk, T* snap, const T* pos, const T* 
     if (!size_ok(n)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (workspace_bytes < 3 * bodies) return NB_ERR_INVALID_ARGUMENT;
-    if (!spans_ok({{jerk, bodies, al}, {snap, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc_in, bodies, al}, {workspace, 3 * bodies, al}})) return NB_ERR_INVALID_ARGUMENT;
     // acc_out: acc_in itself (the evaluation reads the workspace's copy), or an array apart from everything
-    if (acc != acc_in && !spans_ok({{acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc_in, bodies, al}, {workspace, 3 * bodies, al}})) {
+    if (!in_place_or_apart({acc, bodies, al}, acc_in,
+                           {{jerk, bodies, al}, {snap, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc_in, bodies, al}, {workspace, 3 * bodies, al}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     const auto s = static_cast<hipStream_t>(stream);
@@ -87,12 +65,9 @@ int step(T* new_pos, const T* old_pos, T* vel, T* acc, T* jerk, T* snap, T* crac
     if (!size_ok(n)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (workspace_bytes < 3 * bodies) return NB_ERR_INVALID_ARGUMENT;
-    if (!spans_ok({{old_pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al}, {crackle, bodies, al}, {workspace, 3 * bodies, al}})) {
-        return NB_ERR_INVALID_ARGUMENT;
-    }
     // new_positions: old_positions itself, or an array apart from everything
-    if (new_pos != old_pos && !spans_ok({{new_pos, bodies, al}, {old_pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al},
-                                         {crackle, bodies, al}, {workspace, 3 * bodies, al}})) {
+    if (!in_place_or_apart({new_pos, bodies, al}, old_pos,
+                           {{old_pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al}, {crackle, bodies, al}, {workspace, 3 * bodies, al}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     nb::Hermite6Args<T> a{};
@@ -116,7 +91,7 @@ int timestep(const T* acc, const T* jerk, const T* snap, const T* crackle, unsig
 extern "C" {
 
 int nb_hermite6_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     *bytes = static_cast<size_t>(num_bodies) * 12 * sizeof_T;
     return 0;
 }

@@ -2,14 +2,16 @@
 // argument is checked on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never
 // synchronises.  The initial evaluation is hermite_eval.o's (linked in; that object exports nothing).
 #include "../../include/nbody_hip_hermite_block.h"
+#include "capi_check.h"
 #include "hermite_block_kernels.h"
 #include "hermite_kernels.h"
+#include "softening_floor.h"
 
 #include <cmath>
-#include <cstdint>
-#include <initializer_list>
 
 namespace {
+
+using nb::floored, nb::Span, nb::spans_ok;
 
 static_assert(NB_HERMITE_BLOCK_MAX_BODIES == nb::kBlockMaxBodies, "the header's limit is the kernels'");
 static_assert(NB_HERMITE_BLOCK_MAX_LEVEL == nb::kBlockMaxLevel, "the header's deepest level is the kernels'");
@@ -18,27 +20,7 @@ static_assert(sizeof(nb_hermite_block_status_t) == 64 && sizeof(nb::BlockStatus)
 static_assert(sizeof(nb_hermite_block_params_t) == sizeof(nb::BlockParams), "the parameters cross by value");
 static_assert(sizeof(nb::BlockCtrl) == 64, "the control record is 64 bytes");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 bool size_ok(unsigned n) { return n >= 1 && n <= nb::kBlockMaxBodies; }
-
-// no null, every span aligned, no two spans overlapping
-bool spans_ok(std::initializer_list<Span> spans) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (const Span& s : spans) {
-        if (s.p == nullptr || addr(s.p) % s.align != 0) return false;
-    }
-    for (const Span* x = spans.begin(); x != spans.end(); ++x) {
-        for (const Span* y = x + 1; y != spans.end(); ++y) {
-            if (addr(x->p) < addr(y->p) + y->bytes && addr(y->p) < addr(x->p) + x->bytes) return false;
-        }
-    }
-    return true;
-}
 
 bool params_ok(const nb_hermite_block_params_t* p) {
     if (p == nullptr) return false;
@@ -48,8 +30,6 @@ bool params_ok(const nb_hermite_block_params_t* p) {
 }
 
 nb::BlockParams params_of(const nb_hermite_block_params_t* p) { return nb::BlockParams{p->eta, p->eta_start, p->dt_max, p->max_level, 0}; }
-
-template <typename T> T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
 
 template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_block_plan_t* out) {
     if (out == nullptr || !size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
@@ -144,7 +124,7 @@ int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const
 extern "C" {
 
 int nb_hermite_block_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     *bytes = nb::block_layout(num_bodies, sizeof_T).bytes;
     return 0;
 }

@@ -24,6 +24,7 @@
 // arrays, its control record and its softening^2 are fetched per system, wave-uniform, before the loops; the reference mass is the mass of
 // the system's first body (hermite_stream.inc reads it through the system's scalar-load pointer).
 #include "hermite_block_ensemble_kernels.h"
+#include "softening_floor.h"
 
 namespace nb {
 namespace {
@@ -35,9 +36,6 @@ namespace {
 #include "hermite_body.h"
 
 #include "hermite_block_kernels_shared.h"
-
-// softening^2 == 0: the floor of nbody_hip_hermite.h (the i = j term contributes 0, not NaN)
-template <typename T> __device__ __forceinline__ T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
 
 // (read-only for the whole launch -> a scalar load where the index is wave-uniform)
 template <typename V> __device__ __forceinline__ V uniform_load(const V* p, size_t index) {

@@ -3,14 +3,15 @@
 // allocates nothing, takes no lock and never synchronises.  The initial evaluation is hermite_ensemble.o's (linked in; that object
 // exports nothing).
 #include "../../include/nbody_hip_hermite_block_ensemble.h"
+#include "capi_check.h"
 #include "hermite_block_ensemble_kernels.h"
 #include "hermite_ensemble_kernels.h"
 
 #include <cmath>
-#include <cstdint>
-#include <initializer_list>
 
 namespace {
+
+using nb::Span, nb::spans_ok;
 
 static_assert(NB_HERMITE_BLOCK_ENSEMBLE_MAX_BODIES == nb::kBlockEnsembleMaxBodies && NB_HERMITE_BLOCK_ENSEMBLE_MAX_TOTAL == nb::kBlockEnsembleMaxTotal,
               "the header's limits are the kernels'");
@@ -23,12 +24,6 @@ static_assert(sizeof(nb_hermite_block_ensemble_summary_t) == 64 && sizeof(nb::Bl
 static_assert(sizeof(nb_hermite_block_params_t) == sizeof(nb::BlockParams), "the parameters cross by value");
 static_assert(sizeof(nb::BlockCtrl) == 64, "the control record is 64 bytes");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 // N, B and their products: every stage of every call is one launch
 template <typename T> bool size_ok(unsigned n, unsigned b) {
     if (n < 1 || n > nb::kBlockEnsembleMaxBodies || b < 1 || static_cast<unsigned long long>(n) * b > nb::kBlockEnsembleMaxTotal) return false;
@@ -38,20 +33,6 @@ template <typename T> bool size_ok(unsigned n, unsigned b) {
     const unsigned long long schedule = static_cast<unsigned long long>(b) * nb::block_ensemble_blocks(n) * nb::kBlockThreads;
     const nb::EnsembleHermitePlan first = nb::plan_hermite_ensemble<T>(n, b);  // init's evaluation
     return eval <= limit && schedule <= limit && first.grid_blocks * first.block_threads <= limit;
-}
-
-// every span aligned and none null (a span of 0 bytes is an optional array left out: skipped), no two spans overlapping
-bool spans_ok(std::initializer_list<Span> spans) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (const Span& s : spans) {
-        if (s.bytes != 0 && (s.p == nullptr || addr(s.p) % s.align != 0)) return false;
-    }
-    for (const Span* x = spans.begin(); x != spans.end(); ++x) {
-        for (const Span* y = x + 1; y != spans.end(); ++y) {
-            if (x->bytes != 0 && y->bytes != 0 && addr(x->p) < addr(y->p) + y->bytes && addr(y->p) < addr(x->p) + x->bytes) return false;
-        }
-    }
-    return true;
 }
 
 bool params_ok(const nb_hermite_block_params_t* p) {
@@ -100,9 +81,8 @@ bool bind(nb::BlockEnsembleArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t
     const std::uintptr_t          total = static_cast<std::uintptr_t>(l.stride) * b;
     if (workspace_bytes < total) return false;
     const std::uintptr_t count = static_cast<std::uintptr_t>(n) * b, bodies = count * 4 * sizeof(T), al = 4 * sizeof(T);
-    // (the required arrays have at least one element each, so a null one is refused by spans_ok; system_eps2 is the optional one)
     if (!spans_ok({{pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {ticks, count * 8, 8}, {levels, count * 4, 4},
-                   {status, static_cast<std::uintptr_t>(b) * 64, 8}, {workspace, total, 32}, {system_eps2, system_eps2 != nullptr ? b * sizeof(T) : 0, sizeof(T)}})) {
+                   {status, static_cast<std::uintptr_t>(b) * 64, 8}, {workspace, total, 32}, {system_eps2, b * sizeof(T), sizeof(T), Span::optional}})) {
         return false;
     }
     a.pos = pos, a.vel = vel, a.acc = acc, a.jerk = jerk;
@@ -161,7 +141,7 @@ int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const
 extern "C" {
 
 int nb_hermite_block_ensemble_workspace_bytes(unsigned num_bodies, unsigned num_systems, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     if (!(sizeof_T == 4 ? size_ok<float>(num_bodies, num_systems) : size_ok<double>(num_bodies, num_systems))) return NB_ERR_INVALID_ARGUMENT;
     *bytes = nb::block_ensemble_layout(num_bodies, sizeof_T).stride * num_systems;
     return 0;

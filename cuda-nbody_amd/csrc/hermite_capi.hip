@@ -1,40 +1,18 @@
 // hermite_capi.hip -- the extern "C" boundary of libnbody_hip_hermite.so (include/nbody_hip_hermite.h).  Every argument is checked
 // on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_hermite.h"
+#include "capi_check.h"
 #include "hermite_kernels.h"
-
-#include <cstdint>
-#include <initializer_list>
+#include "softening_floor.h"
 
 namespace {
+
+using nb::floored, nb::in_place_or_apart, nb::Span, nb::spans_ok;
 
 static_assert(NB_HERMITE_MAX_BODIES == nb::kHermiteMaxBodies, "the header's limit is the kernels'");
 static_assert(NB_HERMITE_TIMESTEP_SCRATCH_BYTES == nb::kTimestepPartials * sizeof(double), "the header's scratch size is the kernels'");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 bool size_ok(unsigned n) { return n >= 1 && n <= nb::kHermiteMaxBodies; }
-
-// no null, every span aligned, no two spans overlapping
-bool spans_ok(std::initializer_list<Span> spans) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (const Span& s : spans) {
-        if (s.p == nullptr || addr(s.p) % s.align != 0) return false;
-    }
-    for (const Span* x = spans.begin(); x != spans.end(); ++x) {
-        for (const Span* y = x + 1; y != spans.end(); ++y) {
-            if (addr(x->p) < addr(y->p) + y->bytes && addr(y->p) < addr(x->p) + x->bytes) return false;
-        }
-    }
-    return true;
-}
-
-// softening^2 == 0: the floor of the header (the i = j term contributes 0, not NaN)
-template <typename T> T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
 
 template <typename T> int plan_query(unsigned n, nb_hermite_plan_t* out) {
     if (out == nullptr || !size_ok(n)) return NB_ERR_INVALID_ARGUMENT;
@@ -62,9 +40,8 @@ int step(T* new_pos, const T* old_pos, T* vel, T* acc, T* jerk, void* workspace,
     if (!size_ok(n)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (workspace_bytes < 2 * bodies) return NB_ERR_INVALID_ARGUMENT;
-    if (!spans_ok({{old_pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {workspace, 2 * bodies, al}})) return NB_ERR_INVALID_ARGUMENT;
     // new_positions: old_positions itself, or an array apart from everything
-    if (new_pos != old_pos && !spans_ok({{new_pos, bodies, al}, {old_pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {workspace, 2 * bodies, al}})) {
+    if (!in_place_or_apart({new_pos, bodies, al}, old_pos, {{old_pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {workspace, 2 * bodies, al}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     nb::HermiteArgs<T> a{};
@@ -85,7 +62,7 @@ template <typename T> int timestep(const T* acc, const T* jerk, unsigned n, T et
 extern "C" {
 
 int nb_hermite_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     *bytes = static_cast<size_t>(num_bodies) * 8 * sizeof_T;
     return 0;
 }

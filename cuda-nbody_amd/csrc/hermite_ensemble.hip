@@ -11,6 +11,7 @@
 // from that record (clock_decision), which only the clock stage -- after every stage that reads it -- writes; the workgroups of a system
 // that is done or stalled leave after that one scalar load.  No atomics anywhere: the status record is integer sums and exact minima.
 #include "hermite_ensemble_kernels.h"
+#include "softening_floor.h"
 
 namespace nb {
 namespace {
@@ -22,9 +23,6 @@ namespace {
 #include "hermite_body.h"
 
 #include "hermite_ratio.h"
-
-// softening^2 == 0: the floor of nbody_hip_hermite.h (the i = j term contributes 0, not NaN)
-template <typename T> __device__ __forceinline__ T floored(T eps2) { return eps2 == T(0) ? (sizeof(T) == 4 ? T(0x1p-60) : T(0x1p-300)) : eps2; }
 
 // The rule of nb_hermite_ensemble_advance_*, as far as it is a function of the clock before the call: does the system step, with which dt,
 // and is that step its last?

@@ -1,42 +1,22 @@
 // hermite_ensemble_capi.hip -- the extern "C" boundary of libnbody_hip_hermite_ensemble.so (include/nbody_hip_hermite_ensemble.h).  Every
 // argument is checked on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_hermite_ensemble.h"
+#include "capi_check.h"
 #include "hermite_ensemble_kernels.h"
 
-#include <cstdint>
-#include <initializer_list>
-
 namespace {
+
+using nb::in_place_or_apart, nb::Span, nb::spans_ok;
 
 static_assert(NB_HERMITE_ENSEMBLE_MAX_BODIES == nb::kEnsembleHermiteMaxBodies && NB_HERMITE_ENSEMBLE_MAX_TOTAL == nb::kEnsembleHermiteMaxTotal, "the header's limits are the kernels'");
 static_assert(NB_HERMITE_ENSEMBLE_DONE == nb::kClockDone && NB_HERMITE_ENSEMBLE_STALLED == nb::kClockStalled, "the header's flags are the kernels'");
 static_assert(sizeof(nb_hermite_ensemble_clock_t) == sizeof(nb::EnsembleClock) && sizeof(nb_hermite_ensemble_status_t) == sizeof(nb::EnsembleStatus),
               "the header's records are the kernels'");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 template <typename T> bool size_ok(unsigned n, unsigned b) {
     if (n < 1 || n > nb::kEnsembleHermiteMaxBodies || b < 1 || static_cast<unsigned long long>(n) * b > nb::kEnsembleHermiteMaxTotal) return false;
     const nb::EnsembleHermitePlan p = nb::plan_hermite_ensemble<T>(n, b);
     return p.grid_blocks * p.block_threads <= (1ull << 31);  // one launch per stage
-}
-
-// every span aligned and none null (a span of 0 bytes is an optional array left out: skipped), no two spans overlapping
-bool spans_ok(std::initializer_list<Span> spans) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (const Span& s : spans) {
-        if (s.bytes != 0 && (s.p == nullptr || addr(s.p) % s.align != 0)) return false;
-    }
-    for (const Span* x = spans.begin(); x != spans.end(); ++x) {
-        for (const Span* y = x + 1; y != spans.end(); ++y) {
-            if (x->bytes != 0 && y->bytes != 0 && addr(x->p) < addr(y->p) + y->bytes && addr(y->p) < addr(x->p) + x->bytes) return false;
-        }
-    }
-    return true;
 }
 
 // the workspace: the predicted state, the partial minima of every system, the partial status records
@@ -70,21 +50,13 @@ template <typename T> int plan_query(unsigned n, unsigned b, nb_hermite_ensemble
 template <typename T> int eval(T* acc, T* jerk, const T* pos, const T* vel, unsigned n, unsigned b, T eps2, const T* system_eps2, nb_stream_t stream) {
     if (!size_ok<T>(n, b)) return NB_ERR_INVALID_ARGUMENT;
     const Layout<T>      l(n, b);
-    const std::uintptr_t al = 4 * sizeof(T), per_system = system_eps2 != nullptr ? b * sizeof(T) : 0;
-    if (!spans_ok({{acc, l.bodies, al}, {jerk, l.bodies, al}, {pos, l.bodies, al}, {vel, l.bodies, al}, {system_eps2, per_system, sizeof(T)}})) return NB_ERR_INVALID_ARGUMENT;
+    const std::uintptr_t al = 4 * sizeof(T);
+    if (!spans_ok({{acc, l.bodies, al}, {jerk, l.bodies, al}, {pos, l.bodies, al}, {vel, l.bodies, al}, {system_eps2, b * sizeof(T), sizeof(T), Span::optional}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
     nb::EnsembleHermiteArgs<T> a{};
     a.pos = pos, a.vel_in = vel, a.acc = acc, a.jerk = jerk, a.n = n, a.src.eps2 = eps2, a.src.system_eps2 = system_eps2;
     return static_cast<int>(nb::launch_ensemble_eval<T>(a, b, static_cast<hipStream_t>(stream)));
-}
-
-// the arrays of a step, with whatever else the call holds in `more`
-template <typename T>
-bool step_spans_ok(const T* new_pos, const T* old_pos, const T* vel, const T* acc, const T* jerk, const void* workspace, const Layout<T>& l, Span more0, Span more1, Span more2) {
-    const std::uintptr_t al = 4 * sizeof(T);
-    if (!spans_ok({{old_pos, l.bodies, al}, {vel, l.bodies, al}, {acc, l.bodies, al}, {jerk, l.bodies, al}, {workspace, l.total, al}, more0, more1, more2})) return false;
-    // new_positions: old_positions itself, or an array apart from everything
-    return new_pos == old_pos ||
-           spans_ok({{new_pos, l.bodies, al}, {old_pos, l.bodies, al}, {vel, l.bodies, al}, {acc, l.bodies, al}, {jerk, l.bodies, al}, {workspace, l.total, al}, more0, more1, more2});
 }
 
 template <typename T>
@@ -93,8 +65,12 @@ int step(T* new_pos, const T* old_pos, T* vel, T* acc, T* jerk, void* workspace,
     if (!size_ok<T>(n, b)) return NB_ERR_INVALID_ARGUMENT;
     const Layout<T> l(n, b);
     if (workspace_bytes < l.total) return NB_ERR_INVALID_ARGUMENT;
-    const Span table{params, params != nullptr ? static_cast<std::uintptr_t>(b) * 4 * sizeof(T) : 0, 4 * sizeof(T)};
-    if (!step_spans_ok<T>(new_pos, old_pos, vel, acc, jerk, workspace, l, table, Span{nullptr, 0, 1}, Span{nullptr, 0, 1})) return NB_ERR_INVALID_ARGUMENT;
+    const std::uintptr_t al = 4 * sizeof(T);
+    // new_positions: old_positions itself, or an array apart from everything
+    if (!in_place_or_apart({new_pos, l.bodies, al}, old_pos,
+                           {{old_pos, l.bodies, al}, {vel, l.bodies, al}, {acc, l.bodies, al}, {jerk, l.bodies, al}, {workspace, l.total, al}, {params, b * al, al, Span::optional}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
     nb::EnsembleHermiteArgs<T> a{};
     a.state8 = static_cast<const T*>(workspace);
     a.new_pos = new_pos, a.old_pos = old_pos, a.vel = vel, a.acc = acc, a.jerk = jerk, a.n = n, a.src.dt = dt, a.src.eps2 = eps2, a.src.params = params;
@@ -118,9 +94,9 @@ int begin(T* acc, T* jerk, const T* pos, const T* vel, nb_hermite_ensemble_clock
     if (!size_ok<T>(n, b)) return NB_ERR_INVALID_ARGUMENT;
     const Layout<T> l(n, b);
     if (workspace_bytes < l.total) return NB_ERR_INVALID_ARGUMENT;
-    const std::uintptr_t al = 4 * sizeof(T), per_system = system_eps2 != nullptr ? b * sizeof(T) : 0;
+    const std::uintptr_t al = 4 * sizeof(T);
     if (!spans_ok({{acc, l.bodies, al}, {jerk, l.bodies, al}, {pos, l.bodies, al}, {vel, l.bodies, al}, {clocks, b * sizeof(nb::EnsembleClock), 8}, {workspace, l.total, al},
-                   {system_eps2, per_system, sizeof(T)}})) {
+                   {system_eps2, b * sizeof(T), sizeof(T), Span::optional}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     nb::EnsembleHermiteArgs<T> a{};
@@ -138,9 +114,14 @@ int advance(T* new_pos, const T* old_pos, T* vel, T* acc, T* jerk, nb_hermite_en
     if (!size_ok<T>(n, b) || t_stop != t_stop || !(dt_max > 0)) return NB_ERR_INVALID_ARGUMENT;
     const Layout<T> l(n, b);
     if (workspace_bytes < l.total) return NB_ERR_INVALID_ARGUMENT;
-    const Span clock_span{clocks, b * sizeof(nb::EnsembleClock), 8}, status_span{status, status != nullptr ? sizeof(nb::EnsembleStatus) : 0, 8};
-    const Span eps_span{system_eps2, system_eps2 != nullptr ? b * sizeof(T) : 0, sizeof(T)};
-    if (!step_spans_ok<T>(new_pos, old_pos, vel, acc, jerk, workspace, l, clock_span, status_span, eps_span)) return NB_ERR_INVALID_ARGUMENT;
+    const std::uintptr_t al = 4 * sizeof(T);
+    // new_positions: old_positions itself, or an array apart from everything
+    if (!in_place_or_apart({new_pos, l.bodies, al}, old_pos,
+                           {{old_pos, l.bodies, al}, {vel, l.bodies, al}, {acc, l.bodies, al}, {jerk, l.bodies, al}, {workspace, l.total, al},
+                            {clocks, b * sizeof(nb::EnsembleClock), 8}, {status, sizeof(nb::EnsembleStatus), 8, Span::optional},
+                            {system_eps2, b * sizeof(T), sizeof(T), Span::optional}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
     nb::EnsembleHermiteArgs<T> a{};
     a.state8 = static_cast<const T*>(workspace);
     a.new_pos = new_pos, a.old_pos = old_pos, a.vel = vel, a.acc = acc, a.jerk = jerk, a.n = n;
@@ -156,7 +137,7 @@ int advance(T* new_pos, const T* old_pos, T* vel, T* acc, T* jerk, nb_hermite_en
 extern "C" {
 
 int nb_hermite_ensemble_workspace_bytes(unsigned num_bodies, unsigned num_systems, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     if (!(sizeof_T == 4 ? size_ok<float>(num_bodies, num_systems) : size_ok<double>(num_bodies, num_systems))) return NB_ERR_INVALID_ARGUMENT;
     *bytes = sizeof_T == 4 ? Layout<float>(num_bodies, num_systems).total : Layout<double>(num_bodies, num_systems).total;
     return 0;

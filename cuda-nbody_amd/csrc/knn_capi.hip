@@ -1,11 +1,12 @@
 // knn_capi.hip -- the extern "C" boundary of libnbody_hip_knn.so (include/nbody_hip_knn.h).  Every argument is checked on the host before
 // the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_knn.h"
+#include "capi_check.h"
 #include "knn_kernels.h"
 
-#include <cstdint>
-
 namespace {
+
+using nb::Span, nb::spans_ok;
 
 static_assert(NB_NEIGHBOUR_MAX_BODIES == nb::kKnnMaxBodies, "the limit of the neighbour header is the kernels'");
 static_assert(NB_NEIGHBOUR_NONE == nb::kKnnNone, "the header's `none` is the kernels'");
@@ -15,27 +16,7 @@ static_assert(sizeof(nb_knn_structure_t) == 128 && sizeof(nb::KnnStructure) == 1
 static_assert(sizeof(nb::KnnTile) == 72 && sizeof(nb::KnnRing) == 24, "the workspace records");
 static_assert(sizeof(nb_knn_plan_t) == 64, "the plan");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 bool size_ok(unsigned n, unsigned k) { return n >= 1 && n <= nb::kKnnMaxBodies && k >= 1 && k <= nb::kKnnMaxK; }
-
-// every span that is given aligned, no two of them overlapping
-bool spans_ok(const Span* spans, int count) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (int x = 0; x < count; ++x) {
-        if (spans[x].p == nullptr) continue;
-        if (addr(spans[x].p) % spans[x].align != 0) return false;
-        for (int y = x + 1; y < count; ++y) {
-            if (spans[y].p == nullptr) continue;
-            if (addr(spans[x].p) < addr(spans[y].p) + spans[y].bytes && addr(spans[y].p) < addr(spans[x].p) + spans[x].bytes) return false;
-        }
-    }
-    return true;
-}
 
 template <typename T> int plan_query(unsigned n, unsigned k, nb_knn_plan_t* out) {
     if (out == nullptr || !size_ok(n, k)) return NB_ERR_INVALID_ARGUMENT;
@@ -67,9 +48,10 @@ int survey(const T* pos, unsigned n, unsigned k, unsigned* index, T* dist_sq, T*
     const nb::KnnLayout l = nb::knn_layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t N = n, K = k;
-    const Span           spans[] = {{pos, N * 4 * sizeof(T), 4 * sizeof(T)}, {index, N * K * 4, 4},   {dist_sq, N * K * sizeof(T), sizeof(T)},
-                                    {densities, N * sizeof(T), sizeof(T)},   {structure, 128, 8}, {workspace, l.bytes, 32}};
-    if (!spans_ok(spans, 6)) return NB_ERR_INVALID_ARGUMENT;
+    if (!spans_ok({{pos, N * 4 * sizeof(T), 4 * sizeof(T)}, {index, N * K * 4, 4, Span::optional}, {dist_sq, N * K * sizeof(T), sizeof(T), Span::optional},
+                   {densities, N * sizeof(T), sizeof(T), Span::optional}, {structure, 128, 8, Span::optional}, {workspace, l.bytes, 32}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
     nb::KnnArgs<T> a{};
     a.pos = pos, a.n = n, a.k = k, a.index = index, a.dist_sq = dist_sq, a.densities = densities;
     a.structure   = reinterpret_cast<nb::KnnStructure*>(structure);
@@ -86,7 +68,7 @@ int survey(const T* pos, unsigned n, unsigned k, unsigned* index, T* dist_sq, T*
 extern "C" {
 
 int nb_knn_workspace_bytes(unsigned num_bodies, unsigned k, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies, k) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !size_ok(num_bodies, k) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     *bytes = nb::knn_layout(num_bodies, sizeof_T).bytes;
     return 0;
 }

@@ -6,6 +6,7 @@
 #include "../../include/nbody_hip.h"
 #include "../../include/nbody_hip_tuning.h"
 
+#include "capi_check.h"
 #include "nbody_kernels.h"
 #include "rand_stream_guard.h"
 
@@ -294,17 +295,12 @@ constexpr unsigned kEnergyMaxBodies = 1u << 31;
 size_t energy_workspace_bytes(unsigned n) { return std::max(nb::plan_energy<float>(n).workspace_bytes, nb::plan_energy<double>(n).workspace_bytes); }
 
 template <typename T> int energy(const T* pos, const T* vel, unsigned n, void* workspace, size_t workspace_bytes, nb_energy_t* result, T eps2, nb_stream_t stream) {
-    if (!pos || !vel || !workspace || !result || n == 0 || n > kEnergyMaxBodies) return NB_ERR_INVALID_ARGUMENT;
+    if (n == 0 || n > kEnergyMaxBodies) return NB_ERR_INVALID_ARGUMENT;
     const size_t need = energy_workspace_bytes(n);
     if (workspace_bytes < need) return NB_ERR_INVALID_ARGUMENT;
-    const auto addr = [](const void* q) { return reinterpret_cast<std::uintptr_t>(q); };
-    if (!aligned_vec4<T>(pos) || !aligned_vec4<T>(vel) || addr(workspace) % sizeof(double) != 0 || addr(result) % sizeof(double) != 0) return NB_ERR_INVALID_ARGUMENT;
-    const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T);
-    const auto overlap = [&](const void* x, std::uintptr_t x_len, const void* y, std::uintptr_t y_len) { return addr(x) < addr(y) + y_len && addr(y) < addr(x) + x_len; };
-    for (const void* body_array : {static_cast<const void*>(pos), static_cast<const void*>(vel)}) {
-        if (overlap(workspace, need, body_array, bodies) || overlap(result, sizeof(nb_energy_t), body_array, bodies)) return NB_ERR_INVALID_ARGUMENT;
-    }
-    if (overlap(workspace, need, result, sizeof(nb_energy_t))) return NB_ERR_INVALID_ARGUMENT;
+    const std::uintptr_t al = 4 * sizeof(T), bodies = static_cast<std::uintptr_t>(n) * al;
+    // the workspace and the result, apart from each other and from the bodies; positions and velocities are only read
+    if (!nb::spans_ok({{workspace, need, sizeof(double)}, {result, sizeof(nb_energy_t), sizeof(double)}}, {{pos, bodies, al}, {vel, bodies, al}})) return NB_ERR_INVALID_ARGUMENT;
     return static_cast<int>(nb::launch_energy<T>(pos, vel, n, eps2, nb::plan_energy<T>(n), workspace, result, as_stream(stream)));
 }
 static_assert(sizeof(nb_energy_t) == 13 * sizeof(double), "13 doubles, no padding");

@@ -1,12 +1,14 @@
 // neighbour_capi.hip -- the extern "C" boundary of libnbody_hip_neighbour.so (include/nbody_hip_neighbour.h).  Every argument is checked
 // on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never synchronises.
 #include "../../include/nbody_hip_neighbour.h"
+#include "capi_check.h"
 #include "neighbour_kernels.h"
 
 #include <cmath>
-#include <cstdint>
 
 namespace {
+
+using nb::Span, nb::spans_ok;
 
 static_assert(NB_NEIGHBOUR_MAX_BODIES == nb::kNeighbourMaxBodies, "the header's limit is the kernels'");
 static_assert(NB_NEIGHBOUR_NONE == nb::kNeighbourNone, "the header's `none` is the kernels'");
@@ -15,27 +17,7 @@ static_assert(sizeof(nb_neighbour_status_t) == 64 && sizeof(nb::NeighbourStatus)
 static_assert(sizeof(nb::NeighbourCtrl) == 64, "the control record is 64 bytes");
 static_assert(sizeof(nb::NeighbourTile) == 32, "a tile's record is 32 bytes");
 
-struct Span {
-    const void*    p;
-    std::uintptr_t bytes;
-    std::uintptr_t align;
-};
-
 bool size_ok(unsigned n) { return n >= 1 && n <= nb::kNeighbourMaxBodies; }
-
-// every span that is given aligned, no two of them overlapping
-bool spans_ok(const Span* spans, int count) {
-    const auto addr = [](const void* p) { return reinterpret_cast<std::uintptr_t>(p); };
-    for (int x = 0; x < count; ++x) {
-        if (spans[x].p == nullptr) continue;
-        if (addr(spans[x].p) % spans[x].align != 0) return false;
-        for (int y = x + 1; y < count; ++y) {
-            if (spans[y].p == nullptr) continue;
-            if (addr(spans[x].p) < addr(spans[y].p) + spans[y].bytes && addr(spans[y].p) < addr(spans[x].p) + spans[x].bytes) return false;
-        }
-    }
-    return true;
-}
 
 template <typename T> bool scalars_ok(T radius_sq, const T* radii, T eps2) {
     if (radii == nullptr && !(radius_sq >= T(0))) return false;  // (NaN compares false)
@@ -79,9 +61,11 @@ int survey(const T* pos, unsigned n, T radius_sq, const T* radii, T eps2, unsign
     const nb::NeighbourLayout l = nb::neighbour_layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t N = n;
-    const Span           spans[] = {{pos, N * 4 * sizeof(T), 4 * sizeof(T)}, {radii, N * sizeof(T), sizeof(T)}, {nearest, N * 4, 4}, {nearest_d2, N * sizeof(T), sizeof(T)},
-                                    {counts, N * 4, 4},           {potentials, N * sizeof(T), sizeof(T)}, {status, 64, 8},    {workspace, l.bytes, 32}};
-    if (!spans_ok(spans, 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (!spans_ok({{pos, N * 4 * sizeof(T), 4 * sizeof(T)}, {radii, N * sizeof(T), sizeof(T), Span::optional}, {nearest, N * 4, 4, Span::optional},
+                   {nearest_d2, N * sizeof(T), sizeof(T), Span::optional}, {counts, N * 4, 4, Span::optional}, {potentials, N * sizeof(T), sizeof(T), Span::optional},
+                   {status, 64, 8}, {workspace, l.bytes, 32}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
     nb::NeighbourArgs<T> a{};
     a.pos = pos, a.radii = radii, a.radius_sq = radii != nullptr ? T(0) : radius_sq, a.eps2 = eps2, a.n = n;
     a.nearest = nearest, a.nearest_d2 = nearest_d2, a.counts = counts, a.potentials = potentials;
@@ -99,9 +83,10 @@ int lists(const T* pos, unsigned n, T radius_sq, const T* radii, unsigned long l
     const nb::NeighbourLayout l = nb::neighbour_layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t N = n;
-    const Span           spans[] = {{pos, N * 4 * sizeof(T), 4 * sizeof(T)}, {radii, N * sizeof(T), sizeof(T)}, {offsets, (N + 1) * 8, 8},
-                                    {capacity > 0 ? indices : nullptr, static_cast<std::uintptr_t>(capacity) * 4, 4}, {status, 64, 8}, {workspace, l.bytes, 32}};
-    if (!spans_ok(spans, 6)) return NB_ERR_INVALID_ARGUMENT;
+    if (!spans_ok({{pos, N * 4 * sizeof(T), 4 * sizeof(T)}, {radii, N * sizeof(T), sizeof(T), Span::optional}, {offsets, (N + 1) * 8, 8},
+                   {capacity > 0 ? indices : nullptr, static_cast<std::uintptr_t>(capacity) * 4, 4, Span::optional}, {status, 64, 8}, {workspace, l.bytes, 32}})) {
+        return NB_ERR_INVALID_ARGUMENT;
+    }
     nb::NeighbourArgs<T> a{};
     a.pos = pos, a.radii = radii, a.radius_sq = radii != nullptr ? T(0) : radius_sq, a.eps2 = T(0), a.n = n;
     a.offsets = offsets, a.indices = indices, a.capacity = capacity;
@@ -115,7 +100,7 @@ int lists(const T* pos, unsigned n, T radius_sq, const T* radii, unsigned long l
 extern "C" {
 
 int nb_neighbour_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies) || (sizeof_T != 4 && sizeof_T != 8)) return NB_ERR_INVALID_ARGUMENT;
+    if (bytes == nullptr || !size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     *bytes = nb::neighbour_layout(num_bodies, sizeof_T).bytes;
     return 0;
 }

@@ -163,6 +163,25 @@ def test_step_crew_under_thread_sanitizer(tmp_path):
     assert '#include "step_crew.h"' in comm and "class StepCrew" not in comm  # (the product uses THIS class, not a copy of it)
 
 
+def test_capi_check_under_address_and_ub_sanitizers(tmp_path):
+    """The argument check of every extern "C" boundary (csrc/capi_check.h: plain C++, so that the host compiler alone builds this) under
+    AddressSanitizer and UBSan: required and optional null spans, one misaligned span among aligned ones, spans of zero length given
+    and left out, identical spans, spans overlapping by one element at either end, adjacent spans, the in-place-or-apart rule of the
+    steps' outputs, and the written | read form in which the inputs may alias each other.  And the boundaries use THIS check."""
+    exe = tmp_path / "capi_check_test"
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            os.path.join(ROOT, "tests", "capi_check_test.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and "capi check ok" in run.stdout and run.stderr == "", (run.stdout[-2000:], run.stderr[-3000:])
+    csrc = os.path.join(ROOT, "cuda-nbody_amd", "csrc")
+    boundaries = sorted(f for f in os.listdir(csrc) if f.endswith("_capi.hip"))
+    assert len(boundaries) == 10
+    for name in boundaries:
+        text = open(os.path.join(csrc, name)).read()
+        assert '#include "capi_check.h"' in text and "struct Span" not in text and not re.search(r"\bbool spans_ok\(", text), name
+
+
 def test_strict_translation_unit_has_no_fused_multiply_add():
     """The strict kernels must keep separate mul/add (bit-parity with the CPU path): the only v_fma in that
     object are inside the IEEE divide/sqrt expansions, never a contracted a*b+c of ours.  Checked structurally:
