@@ -83,9 +83,9 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
         if (local >= n) continue;
         const size_t i = local;
         vec4         a1, j1, s1;
-        a1.x = LT::get(second[0], k) * m_ref, a1.y = LT::get(second[1], k) * m_ref, a1.z = LT::get(second[2], k) * m_ref, a1.w = 0;
-        j1.x = LT::get(second[3], k) * m_ref, j1.y = LT::get(second[4], k) * m_ref, j1.z = LT::get(second[5], k) * m_ref, j1.w = 0;
-        s1.x = LT::get(second[6], k) * m_ref, s1.y = LT::get(second[7], k) * m_ref, s1.z = LT::get(second[8], k) * m_ref, s1.w = 0;
+        a1.x = LT::get(second[0], k) * out_scale, a1.y = LT::get(second[1], k) * out_scale, a1.z = LT::get(second[2], k) * out_scale, a1.w = 0;
+        j1.x = LT::get(second[3], k) * out_scale, j1.y = LT::get(second[4], k) * out_scale, j1.z = LT::get(second[5], k) * out_scale, j1.w = 0;
+        s1.x = LT::get(second[6], k) * out_scale, s1.y = LT::get(second[7], k) * out_scale, s1.z = LT::get(second[8], k) * out_scale, s1.w = 0;
         if constexpr (STEP) {
             // v1 = v + (a0 + a1) h/2 - (j1 - j0) h^2/10 + (s0 + s1) h^3/120,   x1 = x + (v + v1) h/2 - (a1 - a0) h^2/10 + (j0 + j1) h^3/120
             // c1, the third derivative at the step's end of the quintic through (a, j, s) at both ends:

@@ -78,6 +78,7 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     LT::keep_in_vgpr(eps2);
 
     auto body_j = [&](size_t j, BodyJ<T>& b) { b.p = jp[2 * j], b.v = jp[2 * j + 1]; };  // adjacent: one s_load_dwordx8 / x16
+#define HERMITE_STREAM_UNIT_SUMS  // the partial planes are in units of the reference mass; the finish kernel multiplies
 #include "hermite_stream.inc"
 
     // planes [J][6][slots]: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums

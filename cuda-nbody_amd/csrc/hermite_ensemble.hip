@@ -129,8 +129,8 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         if (local >= n) continue;
         const size_t i = local;
         vec4         a1, j1;
-        a1.x = LT::get(second[0], k) * m_ref, a1.y = LT::get(second[1], k) * m_ref, a1.z = LT::get(second[2], k) * m_ref, a1.w = 0;
-        j1.x = LT::get(second[3], k) * m_ref, j1.y = LT::get(second[4], k) * m_ref, j1.z = LT::get(second[5], k) * m_ref, j1.w = 0;
+        a1.x = LT::get(second[0], k) * out_scale, a1.y = LT::get(second[1], k) * out_scale, a1.z = LT::get(second[2], k) * out_scale, a1.w = 0;
+        j1.x = LT::get(second[3], k) * out_scale, j1.y = LT::get(second[4], k) * out_scale, j1.z = LT::get(second[5], k) * out_scale, j1.w = 0;
         if constexpr (STEP) {
             const vec4 x  = reinterpret_cast<const vec4*>(a.old_pos + origin)[i];
             vec4       v  = reinterpret_cast<const vec4*>(a.vel + origin)[i];
@@ -182,7 +182,7 @@ __device__ __forceinline__ double block_min(double m, double* lds) {
     return lds[0];
 }
 
-// min |a|^2 / |jerk|^2 over kEnsembleTimestepBodies bodies of one system -> partial[system * partials + p].  (The minimum is exact in any
+// min |a| / |jerk| over kEnsembleTimestepBodies bodies of one system -> partial[system * partials + p].  (The minimum is exact in any
 // order, so the partials of the solo call and these give one value.)  With clocks: the systems that take no step in this call are left out.
 template <typename T>
 __global__ __launch_bounds__(256) void hermite_ensemble_timestep_partial(const T* acc, const T* jerk, unsigned n, unsigned partials, EnsembleSource<T> src, bool stepping,
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void hermite_ensemble_timestep_partial(const T
     double         m     = __builtin_inf();
     if (local < n) {
         const size_t i = static_cast<size_t>(system) * n + local;
-        m              = ratio_sq<T>(reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i]);
+        m              = norm_ratio<T>(reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i]);
     }
     m = block_min(m, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = m;
@@ -234,7 +234,7 @@ __device__ __forceinline__ void store_tally(const Tally& t, EnsembleStatus* out)
     *out = s;
 }
 
-// One thread per system: the minimum of the system's partials, dt = eta (T)sqrt(min) -- the expression of hermite_timestep_final -- and
+// One thread per system: the minimum of the system's partials, dt = eta (T)min -- the expression of hermite_timestep_final -- and
 //   dt_out != nullptr   dt_out[s] = dt                                     (nb_hermite_ensemble_timestep_*)
 //   begin               the clock of a run that starts                      (nb_hermite_ensemble_begin_*)
 //   else                the clock after this call's step, by the rule of the header (nb_hermite_ensemble_advance_*), and the block's tally
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void hermite_ensemble_clock(const double* part
         auto next_dt = [&]() {
             double m = __builtin_inf();
             for (unsigned p = 0; p < partials; ++p) m = fmin(m, partial[static_cast<size_t>(s) * partials + p]);
-            return eta * static_cast<T>(__builtin_sqrt(m));
+            return eta * static_cast<T>(m);
         };
         if (dt_out != nullptr) {
             dt_out[s] = next_dt();

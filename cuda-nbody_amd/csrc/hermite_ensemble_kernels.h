@@ -70,7 +70,7 @@ inline unsigned ensemble_status_blocks(unsigned b) { return (b + kEnsembleClockS
 template <typename T> EnsembleHermitePlan plan_hermite_ensemble(unsigned n, unsigned b);
 template <typename T> hipError_t          launch_ensemble_eval(const EnsembleHermiteArgs<T>& a, unsigned b, hipStream_t stream);
 template <typename T> hipError_t          launch_ensemble_step(const EnsembleHermiteArgs<T>& a, unsigned b, T* state8, hipStream_t stream);
-// partial minima of every system -> partial[b * ensemble_partials(n)]; then per system: dt_out[s] = eta (T)sqrt(min) (dt_out != nullptr),
+// partial minima of every system -> partial[b * ensemble_partials(n)]; then per system: dt_out[s] = eta (T)min (dt_out != nullptr),
 // or the clock of the system begun (begin) / advanced by the rule of the header (src.clocks != nullptr), with one partial status record per
 // kEnsembleClockSystems systems; then (status != nullptr) the records summed into status.
 template <typename T>

@@ -85,8 +85,8 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         if (local >= n) continue;
         const size_t i = local;
         vec4         a1, j1;
-        a1.x = LT::get(second[0], k) * m_ref, a1.y = LT::get(second[1], k) * m_ref, a1.z = LT::get(second[2], k) * m_ref, a1.w = 0;
-        j1.x = LT::get(second[3], k) * m_ref, j1.y = LT::get(second[4], k) * m_ref, j1.z = LT::get(second[5], k) * m_ref, j1.w = 0;
+        a1.x = LT::get(second[0], k) * out_scale, a1.y = LT::get(second[1], k) * out_scale, a1.z = LT::get(second[2], k) * out_scale, a1.w = 0;
+        j1.x = LT::get(second[3], k) * out_scale, j1.y = LT::get(second[4], k) * out_scale, j1.z = LT::get(second[5], k) * out_scale, j1.w = 0;
         if constexpr (STEP) {
             const T    dt = a.dt;
             const vec4 x  = reinterpret_cast<const vec4*>(a.old_pos)[i];
@@ -134,7 +134,7 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_timestep_pa
     __shared__ double lds[256];
     double            m = __builtin_inf();
     for (size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256u) {
-        m = fmin(m, ratio_sq<T>(reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i]));
+        m = fmin(m, norm_ratio<T>(reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i]));
     }
     m = block_min(m, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = m;
@@ -145,7 +145,7 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_timestep_fi
     double            m = __builtin_inf();
     for (unsigned i = threadIdx.x; i < count; i += 256u) m = fmin(m, partial[i]);
     m = block_min(m, lds);
-    if (threadIdx.x == 0) dt_out[0] = eta * static_cast<T>(__builtin_sqrt(m));
+    if (threadIdx.x == 0) dt_out[0] = eta * static_cast<T>(m);  // m: the smallest |a| / |jerk| (hermite_ratio.h)
 }
 
 template <typename T, int S, bool STEP> hipError_t launch_s(const HermiteArgs<T>& a, const HermitePlan& p, hipStream_t stream) {

@@ -8,8 +8,15 @@
 //   jp                  the scalar-load pointer whose element 0 is body 0's {x, y, z, m}
 //   pos_base, STRIDE    body j's {x, y, z, m} is the vec4 at pos_base + 4 STRIDE j (an ordinary pointer: the masses, one chunk ahead)
 //   body_j(j, b)        the scalar loads of body j into b
-// It gets: m_ref and, in wave 0 alone (the other waves return inside), second[6]: ax ay az jx jy jz of the lane's bodies i over the
-// workgroup's chunks, in units of m_ref.
+// It gets: m_ref, out_scale and, in wave 0 alone (the other waves return inside), second[6]: ax ay az jx jy jz of the lane's bodies i
+// over the workgroup's chunks, in units of out_scale -- the kernel multiplies by it when it stores.  out_scale is m_ref, as the sums
+// are kept in units of m_ref (a unit-form register sum is added as it is, a mixed one divided by m_ref once) -- unless a wave met a
+// register sum that units of a m_ref below 1 could not hold: behind a first body of 2^-20, jerk sums of heavy close pairs pass FLT_MAX
+// while the jerk itself is representable (tests/test_hermite_domain.py).  That wave multiplies its second-level sum by m_ref and goes
+// on in plain units; before the fold the other waves of the workgroup follow, and out_scale is 1.  Ordinary inputs never get there
+// and keep their bits.  A kernel whose sums are a stored format in units of m_ref -- the partial planes of hermite_block_eval and its
+// ensemble form, which their finish kernels multiply by m_ref -- defines HERMITE_STREAM_UNIT_SUMS in front of the include (undefined
+// here) and has no such escape: its sums hold min(1, |m_ref|) of what they could.
 //
 // A kernel with another interaction defines HERMITE_STREAM_SUMS (the number of sums, NS) and HERMITE_STREAM_INTERACTION (the file that
 // holds its `compute`, in the shape of the one below) in front of the include, which undefines both; it gets second[NS].  Without them
@@ -29,7 +36,7 @@
     const vec  minus3    = LT::splat(T(-3));
     const typename LT::Consts consts = LT::make_consts();
 
-    // sums: ax ay az jx jy jz.  `first`: the register sum of the current form; `second`: the lane's second-level sum, in units of m_ref
+    // sums: ax ay az jx jy jz.  `first`: the register sum of the current form; `second`: the lane's second-level sum
     vec first[NS], second[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) first[q] = second[q] = LT::splat(0);
@@ -91,9 +98,31 @@
     };
 #endif
 #include "wave_groups.inc"
-    T    pending_scale = T(1);  // what `first` is still to be multiplied by
-    auto flush         = [&]() {
-        const vec scale = LT::splat(pending_scale);
+    bool is_unit = true;   // the form `first` holds
+    bool plain   = false;  // (wave-uniform) `second` has left the units of m_ref for plain units
+    auto flush   = [&]() {
+#ifndef HERMITE_STREAM_UNIT_SUMS
+        if (!plain && (m_ref < T(1) && m_ref > T(-1))) {  // counted in a unit below 1 the sums grow: is there room?
+            constexpr T huge = sizeof(T) == 4 ? T(0x1p124) : T(0x1p1020);
+            const T     room = is_unit ? huge : huge * (m_ref < 0 ? -m_ref : m_ref);
+            bool        big  = false;
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+#pragma unroll
+                for (int k = 0; k < W; ++k) {
+                    const T f = LT::get(first[q], k), s = LT::get(second[q], k);
+                    big       = big || (f < 0 ? -f : f) > room || (s < 0 ? -s : s) > huge;
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(big) != 0) {
+                const vec back = LT::splat(m_ref);
+#pragma unroll
+                for (int q = 0; q < NS; ++q) second[q] = second[q] * back;
+                plain = true;
+            }
+        }
+#endif
+        const vec scale = LT::splat(plain ? (is_unit ? m_ref : T(1)) : (is_unit ? T(1) : inv_mref));
 #pragma unroll
         for (int q = 0; q < NS; ++q) second[q] = LT::fma(first[q], scale, second[q]), first[q] = LT::splat(0);
     };
@@ -103,7 +132,6 @@
 
     unsigned c       = c_lo + wave;  // wave w streams chunks c_lo + w, c_lo + w + S, ...
     bool     unit    = c < c_hi ? chunk_is_unit(c) : false;
-    bool     is_unit = true;  // the form `first` holds
     unsigned held    = 0;     // chunks in `first`
     BodyJ<T> b0[U], b1[U];
     if (c < c_hi && n - c * CH >= static_cast<unsigned>(U)) group(static_cast<size_t>(c) * CH, b0);
@@ -118,7 +146,7 @@
         const size_t next = ((c + S) < c_hi && n - (first_j + S * CH) >= static_cast<unsigned>(U)) ? static_cast<size_t>(first_j) + S * CH : first_j;
         if (unit != is_unit || held == kFlushEvery) {
             flush();
-            is_unit = unit, pending_scale = unit ? T(1) : inv_mref, held = 0;
+            is_unit = unit, held = 0;
         }
         if (groups > 0) {
             if (unit) {
@@ -142,6 +170,26 @@
 #include "wave_mates.inc"
     flush();
 
+    // the unit the workgroup's sums are handed over in: m_ref, or 1 when a wave went over to plain units (then all of them do)
+#ifndef HERMITE_STREAM_UNIT_SUMS
+    T out_scale = m_ref;
+    if (S > 1 && m_ref < T(1) && m_ref > T(-1)) {  // (workgroup-uniform: the condition under which flush may go over)
+        __shared__ int went_plain;
+        if (tid == 0) went_plain = 0;
+        __syncthreads();
+        if (plain && lane == 0) went_plain = 1;
+        __syncthreads();
+        if (went_plain != 0 && !plain) {
+            const vec back = LT::splat(m_ref);
+#pragma unroll
+            for (int q = 0; q < NS; ++q) second[q] = second[q] * back;
+        }
+        plain = went_plain != 0;
+    }
+    if (plain) out_scale = T(1);
+#endif
+
 #include "wave_fold.inc"
 #undef HERMITE_STREAM_SUMS
+#undef HERMITE_STREAM_UNIT_SUMS
 #undef HERMITE_STREAM_INTERACTION

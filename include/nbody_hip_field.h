@@ -25,6 +25,17 @@
  * jerk term is m w / s^3 with s at the floor, as the formula says.  The potential uses the same s^2: a coincident pair that is NOT
  * excluded contributes -m * 2^30 (fp32) / -m * 2^150 (fp64) at softening 0.  Callers exclude such a pair by index.
  *
+ * Operand range.  That of nb_hermite_eval_* (nbody_hip_hermite.h, "Operand range"): the sums are held to 5e-6 (fp32) / 1e-14 (fp64)
+ * times a target's sums of term magnitudes A_k, J_k and P_k = sum |m| s^-1, and a single term to 1e-6 / 1e-14 (a, phi) and
+ * 5e-6 / 1e-14 (jerk) of its magnitude, for
+ *   s^2 of every pair in [2^-84, 2^84] (fp32) / [2^-600, 2^600] (fp64);
+ *   masses 0 or of magnitude in [2^-40, 2^40] (fp32) / [2^-100, 2^100] (fp64), any sign;
+ *   velocities with |r| |w| of every pair, and the sums A_k, J_k and P_k, at most 2^126 (fp32) / 2^1022 (fp64).
+ * The sums are in plain units: no source's mass is a unit, and a source's term has the same bits whatever the other sources of its
+ * chunk weigh.  Outside the range nothing is clamped (nbody_hip_hermite.h says what s^-3 does); non-finite inputs are ordinary data,
+ * and exclusion is "mass 0": an excluded source with a NaN or infinite MASS reaches no result of the targets that exclude it, one with
+ * a non-finite coordinate or velocity reaches them as 0 * NaN does.
+ *
  * Exclusion is by INDEX, never by distance.  In the sums of target k, m is m_j, except that it is taken as 0 when j == self_index[k].
  * NB_FIELD_NONE (0xFFFFFFFF), or a NULL array, excludes nobody.  Because exclusion is defined as "mass 0" it is exact: excluding j gives
  * the bits of the same call with m_j = 0 and no exclusion.

@@ -20,8 +20,25 @@
  *   a_i    = sum m_j s^-3 r
  *   jerk_i = sum m_j s^-3 (w - 3 (r.w) s^-2 r)
  * softening_sq == 0 is evaluated with the floor s^2 = r.r + 2^-60 (fp32) / 2^-300 (fp64): the i = j term and any pair of coincident
- * bodies then contribute exactly 0 instead of NaN, and a pair further apart than 2^-18 (fp32; 2^-124 fp64) is not changed by more
+ * bodies with one velocity then contribute exactly 0 instead of NaN, and a pair further apart than 2^-18 (fp32; 2^-124 fp64) is not changed by more
  * than an ulp of s^2.  (With softening_sq > 0 a coincident pair contributes a = 0, jerk = m w / softening^3, as the formulas say.)
+ *
+ * Operand range.  The evaluation is held (tests/test_hermite_domain.py) to 5e-6 (fp32) / 1e-14 (fp64) times a body's sums of term
+ * magnitudes, A_i = sum |m| s^-3 |r| and J_i = sum |m| s^-3 (|w| + 3 |r.w| s^-2 |r|), and a single
+ * term to 1e-6 / 1e-14 (a) and 5e-6 / 1e-14 (jerk) of its magnitude, for
+ *   s^2 = r.r + softening_sq of every pair in [2^-84, 2^84] (fp32) / [2^-600, 2^600] (fp64);
+ *   masses 0 or of magnitude in [2^-40, 2^40] (fp32) / [2^-100, 2^100] (fp64), any sign;
+ *   velocities with |r| |w| of every pair, and the sums A_i and J_i, at most 2^126 (fp32) / 2^1022 (fp64).  At the corner of the
+ *   ranges that go together -- masses of 2^40 at softening_sq = 2^-39 (fp32); 2^100 at 2^-100 (fp64) -- a jerk term is
+ *   2^98.5 |w|, so 500 coherent ones admit |w| up to 2^17.
+ * Inside this range no intermediate of the kernel leaves T's normal range before the result does: sums kept in units of a light
+ * first body's mass go over to plain units before they outgrow T.  Outside it nothing is clamped.  fp32: below s^2 = 2^-85.4, s^-3 overflows and the body's
+ * sums are infinite or NaN; above s^2 = 2^84, s^-3 = s^-1 s^-2 is subnormal and the term is off by up to two units of 2^-149 in
+ * s^-3 -- a bit of precision per 2/3 of a binade -- until it is 0.  fp64 has room on either side of its range (s^-3 leaves it at
+ * s^2 = 2^+-682); the range is what the tests cover.  A sum beyond 2^126 / 2^1022 may overflow to an infinity before the cancelling
+ * terms arrive.
+ * Non-finite inputs are ordinary data: a NaN coordinate or a NaN / infinite mass reaches a and jerk of every body, a NaN velocity
+ * every jerk and no acceleration; masses and velocity .w are never written.
  *
  * Step (nb_hermite_step_*), shared time step dt, P(EC)^1 -- two launches:
  *   predict   x_p = x + v dt + a dt^2/2 + j dt^3/6,   v_p = v + a dt + j dt^2/2                     -> workspace
@@ -33,7 +50,9 @@
  * bits of two separate arrays).  Every other overlap between the arrays of a call is refused.
  *
  * Time step (nb_hermite_timestep_*).  dt_out[0] = eta * min_i |a_i| / |jerk_i| over the bodies with |jerk_i| > 0 and a finite ratio;
- * +inf if there is none.  The result stays on the device: a caller that adapts dt reads one scalar when it wants to.
+ * +inf if there is none.  The result stays on the device: a caller that adapts dt reads one scalar when it wants to.  The rule holds
+ * for every finite a and jerk, subnormal ones included, whose ratio is a finite double and, rounded to T, a normal number or 0:
+ * the two norms are formed from components scaled by a power of two each, so neither |a|^2 nor |jerk|^2 can leave fp64's range.
  *
  * Rules.  The caller owns all memory; a call allocates nothing, keeps no state, takes no lock, never synchronises, never prints and
  * is asynchronous on `stream`, so it may sit inside a graph capture.  No atomics: results are bit-identical from call to call.

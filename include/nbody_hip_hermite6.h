@@ -28,6 +28,17 @@
  * softening_sq == 0 is evaluated with the floor s^2 = r.r + 2^-60 (fp32) / 2^-300 (fp64), as nb_hermite_eval_*: the i = j term then
  * contributes exactly 0 to all three sums instead of NaN, and so does a pair of coincident bodies with the same velocity and acc_in.
  *
+ * Operand range.  That of nb_hermite_eval_* (nbody_hip_hermite.h, "Operand range") with the snap beside the jerk: the evaluation is
+ * held to 5e-6 (fp32) / 1e-14 (fp64) times a body's sums of term magnitudes A_i, J_i and
+ * S_i = sum |m| s^-3 (|b| + 6 |alpha| |J'| + 3 |beta| |r|) (every operand's magnitude, + for every -), for
+ *   s^2 of every pair in [2^-84, 2^84] (fp32) / [2^-600, 2^600] (fp64);
+ *   masses 0 or of magnitude in [2^-40, 2^40] (fp32) / [2^-100, 2^100] (fp64), any sign;
+ *   velocities and acc_in with |r| |w|, |w|^2, |r| |b|, alpha^2 and |beta| of every pair, and the sums A_i, J_i and S_i, at most
+ *   2^126 (fp32) / 2^1022 (fp64).  The snap is the first to get there: at masses of 2^40 and softening_sq = 2^-39 a snap term is of
+ *   the order 2^118 |w|^2.
+ * Outside the range nothing is clamped: what nbody_hip_hermite.h says of s^2, of sums beyond the range and of non-finite inputs
+ * holds here, and a NaN in acc_in reaches every snap and nothing else.
+ *
  * Start of a run (nb_hermite6_init_*).  Evaluates with b = 0 for a and jerk, evaluates again with that a for the snap -- a and jerk of
  * the second pass are the first pass's bits, the sums do not depend on b --, and sets the crackles to 0.  Four launches.
  *
@@ -47,7 +58,11 @@
  *
  * Time step (nb_hermite6_timestep_*).  Aarseth's criterion with the derivatives the scheme holds:
  *   dt_out[0] = eta * sqrt( min_i (|a||s| + |j|^2) / (|j||c| + |s|^2) )
- * over the bodies with a positive denominator and a finite ratio; +inf if there is none.  Per-body arithmetic is fp64 for either T.
+ * over the bodies with a positive denominator and a finite ratio; +inf if there is none.  Per-body arithmetic is fp64 for either T:
+ * plain products of two norms, so the rule holds while |a|^2, |j|^2, |s|^2, |c|^2 and their pairwise products are normal doubles --
+ * always for fp32 inputs, for fp64 inputs with every nonzero norm in [2^-250, 2^250].  Beyond that range THE STEP CAN COME OUT TOO
+ * LARGE: a body whose numerator or denominator overflows is left out of the minimum, and so is one whose denominator underflows to 0;
+ * products that underflow to 0 beside ones that do not count as 0, and the body gives the step the surviving products give.
  * The result stays on the device: a caller that adapts dt reads one scalar when it wants to.
  *
  * Rules.  The caller owns all memory; a call allocates nothing, keeps no state, takes no lock, never synchronises, never prints and

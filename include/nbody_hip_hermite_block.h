@@ -38,6 +38,17 @@
  *  sync        nb_hermite_block_sync_*: every body predicted to status.now_ticks into caller arrays ({x, y, z, m}, {vx, vy, vz, w}):
  *              a synchronised snapshot for output and nb_energy_*; the stored state is only read.
  *
+ * Operand range.  The sums a1, j1 are those of nb_hermite_eval_* and are held to the same bounds over the same range of s^2, masses
+ * and velocities (nbody_hip_hermite.h, "Operand range": s^2 in [2^-84, 2^84] (fp32) / [2^-600, 2^600] (fp64), masses 0 or of magnitude
+ * in [2^-40, 2^40] / [2^-100, 2^100]), with one difference: the partial planes are stored in units of the first body's mass m_0 when
+ * 2^-20 <= |m_0| <= 2^20 (fp32; 2^+-60 fp64), so the sums of term magnitudes A_i and J_i may reach 2^126 min(1, |m_0|) (fp32) /
+ * 2^1022 min(1, |m_0|) (fp64) only: 2^106 behind a first body of 2^-20; beyond that a body's sums may be infinite or NaN.  dt_A and
+ * init's want are plain fp64 expressions -- squares and products of two norms: they follow the rule above while |a|^2, |j|^2,
+ * |a2'|^2, |a3|^2 and their pairwise products are normal doubles -- always in fp32, in fp64 with every nonzero norm in
+ * [2^-250, 2^250].  Beyond that range the result is what the fp64 expression gives: dt_max (a larger step) where it is infinite or
+ * NaN -- a square or product overflowed, or the denominator underflowed to 0; init: also where want is 0 -- and for dt_A a finite
+ * value that can be too small, down to 0 (the deepest level), where the numerator underflowed over a denominator that did not.
+ *
  * Status.  now_ticks: the time of the last block step taken; block_steps; body_steps = sum of n_act; last_active = n_act of the
  * last block step; deepest_level: the deepest level any body held when a block step began; flags.  Written by single lanes with
  * ordinary stores, read by the caller after synchronising the stream.

@@ -26,6 +26,7 @@
  * softening_sq; otherwise it is a device array T[B] of softening^2 per system and the scalar is ignored.  A value of 0 takes the
  * floor of nbody_hip_hermite.h, per system.  Systems of different sizes: pad with bodies of mass +0 behind the real ones, as
  * nbody_hip_hermite_ensemble.h describes; they are stepped like any body and take levels of their own.
+ * The operand range the error bounds hold on is nbody_hip_hermite_block.h's ("Operand range" there), with each system's own first body as its m_0.
  *
  * EACH SYSTEM TAKES EXACTLY THE SOLO BLOCK STEP.  After k calls of nb_hermite_block_ensemble_step_*, system s holds bit for bit what k
  * calls of nb_hermite_block_step_* give on that system alone with the same parameters: positions, velocities, accelerations, jerks,

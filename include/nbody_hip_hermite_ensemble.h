@@ -27,9 +27,10 @@
  *
  * Each system takes exactly the solo step.  With the same dt and softening^2, system s after nb_hermite_ensemble_step_* holds the
  * bits nb_hermite_step_* gives on that system alone; nb_hermite_ensemble_eval_* likewise equals nb_hermite_eval_*, and
- * nb_hermite_ensemble_timestep_* equals nb_hermite_timestep_* (dt_out[s] = eta * (T)sqrt(min_i |a_i|^2 / |jerk_i|^2) over the bodies of
+ * nb_hermite_ensemble_timestep_* equals nb_hermite_timestep_* (dt_out[s] = eta * (T)min_i |a_i| / |jerk_i| over the bodies of
  * system s with |jerk_i| > 0 and a finite ratio; +inf if there is none).  The formulas, the floor that softening_sq == 0 takes (per
- * system) and the predictor-corrector are those of nbody_hip_hermite.h.
+ * system) and the predictor-corrector are those of nbody_hip_hermite.h, and so is the operand range the error bounds hold on
+ * ("Operand range" there; the unit mass a system's unit chunks are recognised by is that system's own first body's).
  *
  * Geometry (nb_hermite_ensemble_plan_*).  Per system it is nb_hermite_plan_*'s, a function of (N, precision) alone: a workgroup owns
  * 64 * bodies_per_lane bodies i of ONE system, workgroup g works on tile g mod groups_per_system of system g / groups_per_system, and
@@ -48,7 +49,7 @@
  * arrays of a call -- the clocks, the status, the parameter arrays and the workspace included -- is refused.
  *
  * The adaptive form.  nb_hermite_ensemble_begin_* evaluates the initial state (accelerations and jerks, as nb_hermite_ensemble_eval_*)
- * and writes one 32-byte clock per system: {time = 0, dt_next = eta * (T)sqrt(min) of that state, dt_last = 0, steps = 0, flags};
+ * and writes one 32-byte clock per system: {time = 0, dt_next = eta * (T)min of that state, dt_last = 0, steps = 0, flags};
  * flags holds NB_HERMITE_ENSEMBLE_STALLED if dt_next is not > 0, else 0.  nb_hermite_ensemble_advance_* then takes ONE step per system
  * that can still move, with that system's own dt, in at most five launches whatever B is.  The rule, per system:
  *   - A system whose flags hold DONE or STALLED is left bit-identical.  Its workgroups leave after one scalar load.

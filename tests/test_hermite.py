@@ -452,7 +452,11 @@ def test_one_step_against_long_double(gpu, dtype):
 def check_one_step(gpu, dtype, n, mass, eps2, dt):
     """an evaluation and one step of cloud(n, mass) against ld_step, stage by stage; shared with tests/test_kernel_matrix.py"""
     pos, vel = cloud(n, dtype, 31 + n, mass)
-    eps2, dt = dtype(eps2), dtype(dt)
+    check_step_of(gpu, pos, vel, dtype(eps2), dtype(dt), f"n {n} {mass}")
+
+
+def check_step_of(gpu, pos, vel, eps2, dt, what):
+    """an evaluation and one step of the T-typed state (pos, vel) against ld_step, stage by stage; shared with tests/test_hermite_domain.py"""
     d = Device(gpu, pos, vel, eps2)
     d.eval()
     acc, jerk = d.get("acc"), d.get("jerk")
@@ -463,8 +467,8 @@ def check_one_step(gpu, dtype, n, mass, eps2, dt):
     for name, g, w, b in zip(("position", "velocity", "acceleration", "jerk"), got, want, bounds):
         err = np.abs(g[:, :3].astype(LD) - w)
         with np.errstate(all="ignore"):
-            print(f"n {n} {mass} dt {dt}: {name} at {float(np.nanmax(np.where(b > 0, err / b, 0))):.3g} of its bound")
-        assert (err <= b).all(), (n, mass, name)
+            print(f"{what} dt {dt}: {name} at {float(np.nanmax(np.where(b > 0, err / b, 0))):.3g} of its bound")
+        assert (err <= b).all(), (what, name)
     assert got[0][:, 3].tobytes() == pos[:, 3].tobytes() and got[1][:, 3].tobytes() == vel[:, 3].tobytes()
     assert not got[2][:, 3].any() and not got[3][:, 3].any()
 

@@ -535,12 +535,17 @@ def test_one_block_step_stage_by_stage_against_long_double(gpu, dtype, n, n_act)
 
 def check_block_stages(gpu, dtype, n, n_act, mass, eta):
     """one block step of n_act due bodies among n (hand_made_schedule), every stage against long double; shared with tests/test_kernel_matrix.py"""
-    tol, u = LD(TOL[dtype]), LD(UNIT_ROUNDOFF[dtype])
     pos, vel = cloud(n, dtype, 1000 + n + n_act, mass)
-    eps2 = dtype(0.01)
+    check_block_stages_of(gpu, pos, vel, dtype(0.01), n_act, mass, eta)
+
+
+def check_block_stages_of(gpu, pos, vel, eps2, n_act, mass, eta, dt_max=0.125):
+    """check_block_stages of the T-typed state (pos, vel); `mass` names it in the messages; shared with tests/test_hermite_domain.py"""
+    dtype, n = pos.dtype.type, pos.shape[0]
+    tol, u = LD(TOL[dtype]), LD(UNIT_ROUNDOFF[dtype])
     now, max_level, active, levels, ticks = hand_made_schedule(n, n_act, n * 7 + n_act)
-    params = gpu.HermiteBlockParams(eta, 0.01, 0.125, max_level, 0)
-    q = 0.125 * 2.0 ** -max_level
+    params = gpu.HermiteBlockParams(eta, 0.01, dt_max, max_level, 0)
+    q = dt_max * 2.0 ** -max_level
     acc, jerk = hermite_eval(gpu, pos, vel, eps2)
     d = BlockDevice(gpu, pos, vel, eps2, params, ws_fill=np.nan)
     d.put("acc", acc), d.put("jerk", jerk), d.put("ticks", ticks.astype(np.uint64)), d.put("levels", levels.astype(np.int32))
@@ -591,7 +596,8 @@ def check_block_stages(gpu, dtype, n, n_act, mass, eta):
     assert got[0][:, 3].tobytes() == pos[:, 3].tobytes() and got[1][:, 3].tobytes() == vel[:, 3].tobytes()
     assert not got[2][:, 3].any() and not got[3][:, 3].any()
     # the stored sums are the partial planes added in range order, times the reference mass
-    m_ref = pos[0, 3] if 2.0 ** -20 <= abs(pos[0, 3]) <= 2.0 ** 20 else dtype(1)
+    window = 2.0 ** (20 if dtype == np.float32 else 60)  # (usable_unit, csrc/nbody_lane.h)
+    m_ref = pos[0, 3] if 1 / window <= abs(pos[0, 3]) <= window else dtype(1)
     total = planes[0, :, :n_act].copy()
     for r in range(1, planes.shape[0]):
         total += planes[r, :, :n_act]
