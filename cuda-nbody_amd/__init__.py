@@ -46,6 +46,8 @@ HERMITE_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_ENSEMBLE_LIB", os.
 # Block time steps of many independent systems, one launch per stage (include/nbody_hip_hermite_block_ensemble.h) are a tenth, loaded by
 # hermite_block_ensemble_lib().
 HERMITE_BLOCK_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite_block_ensemble.so"))
+# 6th-order Hermite steps with block time steps (include/nbody_hip_hermite6_block.h) are a twelfth, loaded by hermite6_block_lib().
+HERMITE6_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_BLOCK_LIB", os.path.join(HERE, "libnbody_hip_hermite6_block.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -329,6 +331,21 @@ HERMITE_BLOCK_SIGNATURES = {
     "nb_hermite_block_sync_f64": (_ci, [_vp] * 8 + [_cu, _P(HermiteBlockParams), _vp]),
 }
 
+# include/nbody_hip_hermite6_block.h: exported by libnbody_hip_hermite6_block.so, and nothing else is.  Parameters, status and plan
+# records are the 4th-order block library's.
+_block6_state = [_vp] * 10 + [_sz, _cu]  # positions velocities accelerations jerks snaps crackles ticks levels status workspace, workspace_bytes, N
+HERMITE6_BLOCK_SIGNATURES = {
+    "nb_hermite6_block_workspace_bytes": (_ci, [_cu, _cu, _P(_sz)]),
+    "nb_hermite6_block_plan_f32": (_ci, [_cu, _cu, _P(HermiteBlockPlan)]),
+    "nb_hermite6_block_plan_f64": (_ci, [_cu, _cu, _P(HermiteBlockPlan)]),
+    "nb_hermite6_block_init_f32": (_ci, _block6_state + [_cf, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_init_f64": (_ci, _block6_state + [_cd, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_step_f32": (_ci, _block6_state + [_cf, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite6_block_step_f64": (_ci, _block6_state + [_cd, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite6_block_sync_f32": (_ci, [_vp] * 10 + [_cu, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_sync_f64": (_ci, [_vp] * 10 + [_cu, _P(HermiteBlockParams), _vp]),
+}
+
 
 # include/nbody_hip_neighbour.h: exported by libnbody_hip_neighbour.so, and nothing else is
 class NeighbourStatus(ctypes.Structure):
@@ -554,6 +571,11 @@ def hermite_block_ensemble_lib() -> ctypes.CDLL:
 def hermite_block_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite_block.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
     return _load(HERMITE_BLOCK_LIB_PATH, HERMITE_BLOCK_SIGNATURES)
+
+
+def hermite6_block_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite6_block.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    return _load(HERMITE6_BLOCK_LIB_PATH, HERMITE6_BLOCK_SIGNATURES)
 
 
 def neighbour_lib() -> ctypes.CDLL:
@@ -1160,6 +1182,7 @@ class HermiteBlockSystem(_HermiteState):
     step would pass t_stop; ``snapshot()`` is the synchronised state at the status time; ``status()`` the status record."""
 
     _library, _prefix = staticmethod(hermite_block_lib), "nb_hermite_block_"
+    _query = staticmethod(hermite_block_workspace_bytes)
 
     def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None, eta=0.02, eta_start=0.01, dt_max=0.125, max_level=30):
         super().__init__(dtype)
@@ -1167,7 +1190,7 @@ class HermiteBlockSystem(_HermiteState):
         self.softening_sq = self.dtype.type(self._softening_or_default(softening_sq))
         self.params = HermiteBlockParams(float(eta), float(eta_start), float(dt_max), int(max_level), 0)
         self.tick = float(dt_max) * 2.0 ** -int(max_level)
-        self._workspace_bytes = hermite_block_workspace_bytes(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
+        self._workspace_bytes = self._query(self.num_bodies, self.dtype)  # refuses the sizes the step refuses
         self.shape = (self.num_bodies, 4)
         nbytes = 4 * self.num_bodies * self.dtype.itemsize
         self._pos, self._vel, self._acc, self._jerk, self._pos_out, self._vel_out = (DeviceBuffer(nbytes) for _ in range(6))
@@ -1224,6 +1247,49 @@ class HermiteBlockSystem(_HermiteState):
 
     def get_levels(self) -> np.ndarray:
         return self._levels.download(np.empty(self.num_bodies, dtype=np.int32))
+
+
+def hermite6_block_plan(num_bodies: int, num_active: int, dtype=np.float32) -> HermiteBlockPlan:
+    """nb_hermite6_block_plan_*: the geometry of a 6th-order block step of `num_active` of `num_bodies` bodies"""
+    return _plan(hermite6_block_lib, "hermite6_block", HermiteBlockPlan, dtype, num_bodies, num_active)
+
+
+def hermite6_block_workspace_bytes(num_bodies: int, dtype=np.float32) -> int:
+    return _query_workspace_bytes(hermite6_block_lib, "hermite6_block", dtype, num_bodies)
+
+
+class Hermite6BlockSystem(HermiteBlockSystem):
+    """One system of N bodies on the device, stepped by the 6th-order Hermite scheme with block time steps of
+    include/nbody_hip_hermite6_block.h.
+
+    HermiteBlockSystem's arrays and methods plus the snaps and crackles.  eta sits inside the root of dt_A as there, and eta = 0.2 here
+    does what eta = 0.02 does in the 4th-order scheme."""
+
+    _library, _prefix = staticmethod(hermite6_block_lib), "nb_hermite6_block_"
+    _query = staticmethod(hermite6_block_workspace_bytes)
+
+    def __init__(self, num_bodies: int, dtype=np.float32, softening_sq=None, eta=0.2, eta_start=0.01, dt_max=0.125, max_level=30):
+        super().__init__(num_bodies, dtype, softening_sq, eta, eta_start, dt_max, max_level)
+        nbytes = 4 * self.num_bodies * self.dtype.itemsize
+        self._snap, self._crackle = DeviceBuffer(nbytes), DeviceBuffer(nbytes)
+
+    def _buffers(self):
+        return super()._buffers() + [self._snap, self._crackle]
+
+    def _state_args(self):
+        return (self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._ticks.ptr, self._levels.ptr, self._status.ptr,
+                self._workspace.ptr, self._workspace_bytes, self.num_bodies, self._scalar(self.softening_sq), ctypes.byref(self.params))
+
+    def sync(self, stream=None) -> None:
+        """the synchronised snapshot, left on the device: snapshot_ptrs() for nb_energy_*"""
+        self._call("sync", self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr,
+                   self._ticks.ptr, self._status.ptr, self.num_bodies, ctypes.byref(self.params), stream)
+
+    def get_snaps(self) -> np.ndarray:
+        return self._download(self._snap)
+
+    def get_crackles(self) -> np.ndarray:
+        return self._download(self._crackle)
 
 
 def hermite_block_ensemble_plan(num_bodies: int, num_systems: int, num_active: int, dtype=np.float32) -> HermiteBlockEnsemblePlan:

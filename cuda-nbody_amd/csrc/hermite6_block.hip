@@ -1,0 +1,340 @@
+// hermite6_block.hip -- the kernels of libnbody_hip_hermite6_block.so (include/nbody_hip_hermite6_block.h): 6th-order Hermite steps
+// (Nitadori & Makino 2008) with block time steps.  gfx950 only; FMA contraction on.
+//
+// One block step is the six launches of hermite_block.hip, no atomics, every word written by one lane:
+//   block_min_partial      per workgroup, the minimum of tick + ticks(level) (and the deepest level held)    (hermite_block_schedule.inc)
+//   block6_predict_count   block_predict_count with the 6th-order predictor: `now`, t_stop and the flag; every body predicted to `now`
+//                          into the workspace, three vec4 each {x_p, m, v_p, 0, a_p, 0}; active bodies counted per workgroup
+//   block_scan             ONE workgroup: exclusive prefix of the counts in index order, n_act, the status counters            (.inc)
+//   block_scatter          the active list, ascending body index                                                               (.inc)
+//   hermite6_block_eval    the hot path, see below
+//   hermite6_block_finish  one lane per active slot: J partials in index order, corrector, crackle, dt_A, new level, the stored state
+// A step that would pass t_stop leaves go = 0 in the control record and the four launches after it return at once.
+//
+// hermite6_block_eval<T, S> is hermite_block_eval's distribution of work -- a workgroup owns one tile of 64 W ACTIVE bodies, gathered
+// through the active list from the predicted state, and one of J contiguous ranges of the chunks of bodies j; (tile, range) from n_act,
+// read on the device; wave 0 stores the partial sums, in units of the reference mass, to planes [J][9][slots] -- around hermite6_eval's
+// streaming loops: hermite_stream.inc with nine sums and hermite6_interaction.inc, a body j three adjacent vec4 by scalar loads, 47 / 48
+// v_pk_* + 2 v_rsq_f32 per packed pair, no LDS, barrier or scratch inside the loops.  Compiled, as hermite6_eval, for 4 (fp32) / 3 (fp64)
+// waves per SIMD.  hermite6_block_finish adds the planes (range_sum.inc) and applies hermite6_eval's corrector with the body's own step.
+#include "hermite6_block_kernels.h"
+#include "hermite6_kernels.h"
+
+namespace nb {
+namespace {
+
+#include "nbody_lane.h"
+
+#include "hermite_powers.h"
+
+template <typename T> struct BodyJ {
+    typename Lane<T>::raw4 p, v, a;  // {x, y, z, m}, {vx, vy, vz, -}, {ax, ay, az, -} in scalar registers
+};
+
+#include "hermite_block_kernels_shared.h"
+
+#include "hermite_block_schedule.inc"
+
+// the waves per SIMD hermite6_eval is compiled for (hermite6_eval.hip says why); U is hermite6_unroll_for (hermite6_kernels.h)
+template <typename T> inline constexpr int kWavesPerSimd = sizeof(T) == 8 ? 3 : 4;
+
+template <typename T, int S>
+__global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd<T>, kWavesPerSimd<T>))) void hermite6_block_eval(const T* state12, const unsigned* active,
+                                                                                                                                    const BlockCtrl* ctrl, T* partial, unsigned n,
+                                                                                                                                    T eps2_in) {
+    using LT             = Lane<T>;
+    using vec4           = typename LT::vec4;
+    using vec            = typename LT::vec;
+    using raw4           = typename LT::raw4;
+    using bits           = typename LT::bits;
+    constexpr int W      = LT::W;  // bodies i per lane
+    constexpr int U      = hermite6_unroll_for<T>();
+    constexpr int STRIDE = 3;  // vec4 per body of state12
+    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx4/x8/x16
+
+    if (ctrl->go == 0) return;
+    const unsigned  n_act = ctrl->n_act;
+    const BlockGeom geom  = stream_geometry(n, n_act, 64 * W, kBlockTarget);
+    if (blockIdx.x >= geom.tiles * geom.ranges) return;
+    const unsigned ranges = geom.ranges;
+    const unsigned tile   = blockIdx.x / ranges;
+    const unsigned range  = blockIdx.x % ranges;
+    const unsigned slots  = geom.tiles * (64 * W);
+
+    const T* const   pos_base = state12;
+    const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state12));
+    const int        tid  = threadIdx.x;
+    const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int        lane = tid & 63;
+
+    // bodies i of this lane: slots tile_base + k*64 + lane of the active list
+    const unsigned tile_base = tile * (64 * W);
+    vec            px, py, pz, vx, vy, vz, ax, ay, az;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const unsigned slot = tile_base + k * 64 + lane;
+        const size_t   i    = active[slot < n_act ? slot : n_act - 1];
+        const vec4     p    = reinterpret_cast<const vec4*>(state12)[3 * i];
+        const vec4     v    = reinterpret_cast<const vec4*>(state12)[3 * i + 1];
+        const vec4     b    = reinterpret_cast<const vec4*>(state12)[3 * i + 2];
+        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
+        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
+        LT::set(ax, k, b.x), LT::set(ay, k, b.y), LT::set(az, k, b.z);
+    }
+    vec eps2 = LT::splat(eps2_in);
+    LT::keep_in_vgpr(eps2);
+
+    auto body_j = [&](size_t j, BodyJ<T>& b) { b.p = jp[3 * j], b.v = jp[3 * j + 1], b.a = jp[3 * j + 2]; };  // adjacent
+#define HERMITE_STREAM_SUMS 9
+#define HERMITE_STREAM_INTERACTION "hermite6_interaction.inc"
+#define HERMITE_STREAM_UNIT_SUMS  // the partial planes are in units of the reference mass; the finish kernel multiplies
+#include "hermite_stream.inc"
+
+    // planes [J][9][slots]: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) partial[(static_cast<size_t>(range) * 9 + q) * slots + tile_base + k * 64 + lane] = LT::get(second[q], k);
+    }
+}
+
+// ---- the predictor ------------------------------------------------------------------------------------------------------------------------
+
+// One body to dt, Horner to the crackle: the expressions of hermite6_predict (hermite6_eval.hip).  dt = 0 gives the stored bits.
+template <typename T> struct Predicted6 {
+    typename Lane<T>::vec4 x, v, a;  // {x_p, m}, {v_p, 0}, {a_p, 0}
+};
+template <typename T>
+__device__ __forceinline__ Predicted6<T> predict6_body(const typename Lane<T>::vec4& x, const typename Lane<T>::vec4& v, const typename Lane<T>::vec4& a,
+                                                       const typename Lane<T>::vec4& j, const typename Lane<T>::vec4& s, const typename Lane<T>::vec4& c, T dt) {
+    const T       h2 = dt * T(0.5), h3 = dt * (T(1) / T(3)), h4 = dt * T(0.25), h5 = dt * T(0.2);
+    Predicted6<T> o;
+    auto          component = [&](T xq, T vq, T aq, T jq, T sq, T cq, T& xpq, T& vpq, T& apq) {
+        xpq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, __builtin_fma(h4, __builtin_fma(h5, cq, sq), jq), aq), vq), xq);
+        vpq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, __builtin_fma(h4, cq, sq), jq), aq), vq);
+        apq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, cq, sq), jq), aq);
+    };
+    component(x.x, v.x, a.x, j.x, s.x, c.x, o.x.x, o.v.x, o.a.x);
+    component(x.y, v.y, a.y, j.y, s.y, c.y, o.x.y, o.v.y, o.a.y);
+    component(x.z, v.z, a.z, j.z, s.z, c.z, o.x.z, o.v.z, o.a.z);
+    o.x.w = x.w, o.v.w = 0, o.a.w = 0;
+    return o;
+}
+
+template <typename T> __global__ __launch_bounds__(256) void block6_predict_count(Block6Args<T> a, unsigned partials) {
+    using vec4 = typename Lane<T>::vec4;
+    __shared__ unsigned long long lds_next[256];
+    __shared__ int                lds_level[256];
+    __shared__ unsigned           wave_count[4];
+    MinLevel                      m{~0ull, 0};
+    for (unsigned i = threadIdx.x; i < partials; i += 256u) {
+        const unsigned long long next = a.min_part[i];
+        const int                k    = a.lvl_part[i];
+        if (next < m.next) m.next = next;
+        if (k > m.level) m.level = k;
+    }
+    m                            = block_fold(m, lds_next, lds_level);
+    const unsigned long long now = m.next;
+    const double             q   = tick_length(a.p);
+    const bool               go  = static_cast<double>(now) * q <= a.t_stop;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.ctrl->now = now, a.ctrl->go = go ? 1u : 0u;
+        if (!go) a.ctrl->n_act = 0;
+        const unsigned flags    = a.status->flags;
+        a.status->flags         = go ? (flags & ~kBlockStopped) : (flags | kBlockStopped);
+        const int deepest       = a.status->deepest_level;
+        a.status->deepest_level = m.level > deepest ? m.level : deepest;
+    }
+    if (!go) return;
+    const unsigned i      = blockIdx.x * 256u + threadIdx.x;
+    bool           active = false;
+    if (i < a.n) {
+        const unsigned long long tick = a.ticks[i];
+        active                        = tick + ticks_of(a.levels[i], a.p.max_level) == now;
+        const T                  dt   = static_cast<T>(static_cast<double>(now - tick) * q);
+        const Predicted6<T>      o    = predict6_body<T>(reinterpret_cast<const vec4*>(a.pos)[i], reinterpret_cast<const vec4*>(a.vel)[i], reinterpret_cast<const vec4*>(a.acc)[i],
+                                                         reinterpret_cast<const vec4*>(a.jerk)[i], reinterpret_cast<const vec4*>(a.snap)[i],
+                                                         reinterpret_cast<const vec4*>(a.crackle)[i], dt);
+        vec4* const              out  = reinterpret_cast<vec4*>(a.state12) + 3 * static_cast<size_t>(i);
+        out[0] = o.x, out[1] = o.v, out[2] = o.a;
+    }
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
+    __syncthreads();
+    if (threadIdx.x == 0) a.counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+}
+
+// ---- the finish -----------------------------------------------------------------------------------------------------------------------
+
+// Aarseth's step with the derivatives the scheme holds, from the stored T-typed a1, j1, s1, c1, in fp64
+// (include/nbody_hip_hermite6_block.h)
+template <typename V> __device__ __forceinline__ double aarseth6_dt(const V& a1, const V& j1, const V& s1, const V& c1, double eta, double dt_max) {
+    const double n_a = norm3(a1.x, a1.y, a1.z), n_j = norm3(j1.x, j1.y, j1.z), n_s = norm3(s1.x, s1.y, s1.z), n_c = norm3(c1.x, c1.y, c1.z);
+    const double dt  = __builtin_sqrt(eta * (n_a * n_s + n_j * n_j) / (n_j * n_c + n_s * n_s));
+    return (dt == dt && dt - dt == 0) ? dt : dt_max;
+}
+
+template <typename T> __global__ __launch_bounds__(256) void hermite6_block_finish(Block6Args<T> a) {
+    using vec4 = typename Lane<T>::vec4;
+    constexpr unsigned per_tile = 64 * Lane<T>::W;
+    if (a.ctrl->go == 0) return;
+    const unsigned n_act = a.ctrl->n_act;
+    const unsigned slot  = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= n_act) return;
+    const BlockGeom          geom  = stream_geometry(a.n, n_act, per_tile, kBlockTarget);
+    const size_t             slots = static_cast<size_t>(geom.tiles) * per_tile;
+    const unsigned long long now   = a.ctrl->now;
+    const size_t             i     = a.active[slot];
+    // sum[9]: the J ranges' partial sums of this slot, in range order
+    constexpr int            NS      = 9;
+    const T* const           partial = a.partial;
+    const unsigned           ranges  = geom.ranges;
+#include "range_sum.inc"
+    const T m_first = a.state12[3];
+    const T m_ref   = usable_unit(m_first) ? m_first : T(1);
+    vec4    a1, j1, s1;
+    a1.x = sum[0] * m_ref, a1.y = sum[1] * m_ref, a1.z = sum[2] * m_ref, a1.w = 0;
+    j1.x = sum[3] * m_ref, j1.y = sum[4] * m_ref, j1.z = sum[5] * m_ref, j1.w = 0;
+    s1.x = sum[6] * m_ref, s1.y = sum[7] * m_ref, s1.z = sum[8] * m_ref, s1.w = 0;
+
+    int                      k     = a.levels[i];
+    k                              = k < 0 ? 0 : (k > a.p.max_level ? a.p.max_level : k);
+    const double             q     = tick_length(a.p);
+    const unsigned long long own   = 1ull << (a.p.max_level - k);
+    const double             dt_i  = static_cast<double>(own) * q;
+    // the corrector and the crackle of nb_hermite6_step_* (hermite6_eval's epilogue), with the body's own step
+    const T    h = static_cast<T>(dt_i), h2 = h * T(0.5), hh = h * h, t10 = hh * T(0.1), h3 = hh * h, t120 = h3 * (T(1) / T(120));
+    const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
+    vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
+    const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
+    const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
+    const vec4 s0 = reinterpret_cast<const vec4*>(a.snap)[i];
+    vec4       x1, c1;
+    auto       component = [&](T xq, T& vq, T a0q, T j0q, T s0q, T a1q, T j1q, T s1q, T& x1q, T& c1q) {
+        const T v1 = vq + __builtin_fma(h2, a0q + a1q, __builtin_fma(t120, s0q + s1q, -t10 * (j1q - j0q)));
+        x1q        = xq + __builtin_fma(h2, vq + v1, __builtin_fma(t120, j0q + j1q, -t10 * (a1q - a0q)));
+        const T d0 = __builtin_fma(-h2 * h, s0q, __builtin_fma(-h, j0q, a1q - a0q));
+        const T d1 = __builtin_fma(-h, s0q, j1q - j0q) * h;
+        const T d2 = (s1q - s0q) * hh;
+        c1q        = __builtin_fma(T(9), d2, __builtin_fma(T(-36), d1, T(60) * d0)) / h3;
+        vq         = v1;
+    };
+    component(x.x, v.x, a0.x, j0.x, s0.x, a1.x, j1.x, s1.x, x1.x, c1.x);
+    component(x.y, v.y, a0.y, j0.y, s0.y, a1.y, j1.y, s1.y, x1.y, c1.y);
+    component(x.z, v.z, a0.z, j0.z, s0.z, a1.z, j1.z, s1.z, x1.z, c1.z);
+    x1.w = x.w, c1.w = 0;
+    reinterpret_cast<vec4*>(a.pos)[i]     = x1;
+    reinterpret_cast<vec4*>(a.vel)[i]     = v;
+    reinterpret_cast<vec4*>(a.acc)[i]     = a1;
+    reinterpret_cast<vec4*>(a.jerk)[i]    = j1;
+    reinterpret_cast<vec4*>(a.snap)[i]    = s1;
+    reinterpret_cast<vec4*>(a.crackle)[i] = c1;
+
+    const double dt_a = aarseth6_dt(a1, j1, s1, c1, a.p.eta, a.p.dt_max);
+    if (dt_a < dt_i) {
+        while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > dt_a) ++k;
+    } else if (dt_a >= 2.0 * dt_i && k > 0 && now % (2 * own) == 0) {
+        --k;
+    }
+    a.levels[i] = k;
+    a.ticks[i]  = now;
+}
+
+// init: levels from the accelerations and jerks nb_hermite6_init's launches left, ticks 0, the status record cleared
+template <typename T> __global__ __launch_bounds__(256) void block6_init_levels(Block6Args<T> a) {
+    using vec4       = typename Lane<T>::vec4;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0) {
+        BlockStatus s{};
+        *a.status = s;
+        BlockCtrl c{};
+        *a.ctrl = c;
+    }
+    if (i >= a.n) return;
+    const vec4   acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
+    const double want0 = a.p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
+    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : a.p.dt_max;
+    const double q     = tick_length(a.p);
+    int          k     = 0;
+    while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > want) ++k;
+    a.levels[i] = k;
+    a.ticks[i]  = 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void block6_sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const T* snap, const T* crackle,
+                                                   const unsigned long long* ticks, const BlockStatus* status, unsigned n, BlockParams p) {
+    using vec4       = typename Lane<T>::vec4;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long now = status->now_ticks, tick = ticks[i];
+    const T                  dt  = static_cast<T>(static_cast<double>(now > tick ? now - tick : 0ull) * tick_length(p));
+    const vec4               v   = reinterpret_cast<const vec4*>(vel)[i];
+    Predicted6<T>            o   = predict6_body<T>(reinterpret_cast<const vec4*>(pos)[i], v, reinterpret_cast<const vec4*>(acc)[i], reinterpret_cast<const vec4*>(jerk)[i],
+                                                    reinterpret_cast<const vec4*>(snap)[i], reinterpret_cast<const vec4*>(crackle)[i], dt);
+    o.v.w                               = v.w;
+    reinterpret_cast<vec4*>(pos_out)[i] = o.x;
+    reinterpret_cast<vec4*>(vel_out)[i] = o.v;
+}
+
+template <typename T, int S> hipError_t launch_eval_s(const Block6Args<T>& a, unsigned groups, hipStream_t stream) {
+    hipLaunchKernelGGL((hermite6_block_eval<T, S>), dim3(groups), dim3(64 * S), 0, stream, static_cast<const T*>(a.state12), static_cast<const unsigned*>(a.active),
+                       static_cast<const BlockCtrl*>(a.ctrl), a.partial, a.n, a.eps2);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+template <typename T> hipError_t launch_block6_init(const Block6Args<T>& a, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block6_init_levels<T>), dim3((a.n + 255u) / 256u), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T> hipError_t launch_block6_step(const Block6Args<T>& a, hipStream_t stream) {
+    constexpr unsigned per_tile = 64 * Lane<T>::W;
+    const unsigned     blocks   = (a.n + 255u) / 256u;
+    const unsigned     partials = blocks < kBlockMinPartials ? blocks : kBlockMinPartials;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(block_min_partial, dim3(partials), dim3(256), 0, stream, static_cast<const unsigned long long*>(a.ticks), static_cast<const int*>(a.levels), a.n,
+                       a.p.max_level, a.min_part, a.lvl_part);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL((block6_predict_count<T>), dim3(blocks), dim3(256), 0, stream, a, partials);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL(block_scan, dim3(1), dim3(1024), 0, stream, a.counts, blocks, a.ctrl, a.status);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    hipLaunchKernelGGL(block_scatter, dim3(blocks), dim3(256), 0, stream, static_cast<const unsigned long long*>(a.ticks), static_cast<const int*>(a.levels),
+                       static_cast<const unsigned*>(a.counts), static_cast<const BlockCtrl*>(a.ctrl), a.active, a.n, a.p.max_level);
+    if (const auto err = hipGetLastError(); err != hipSuccess) return err;
+    const unsigned groups = block_launch_groups(a.n, per_tile);
+    hipError_t     err    = hipErrorInvalidValue;
+    switch (block_waves(a.n)) {
+        case 1: err = launch_eval_s<T, 1>(a, groups, stream); break;
+        case 2: err = launch_eval_s<T, 2>(a, groups, stream); break;
+        case 4: err = launch_eval_s<T, 4>(a, groups, stream); break;
+        case 8: err = launch_eval_s<T, 8>(a, groups, stream); break;
+        default: break;
+    }
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((hermite6_block_finish<T>), dim3(blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block6_sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const T* snap, const T* crackle, const unsigned long long* ticks,
+                              const BlockStatus* status, unsigned n, const BlockParams& p, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((block6_sync<T>), dim3((n + 255u) / 256u), dim3(256), 0, stream, pos_out, vel_out, pos, vel, acc, jerk, snap, crackle, ticks, status, n, p);
+    return hipGetLastError();
+}
+
+template hipError_t launch_block6_init<float>(const Block6Args<float>&, hipStream_t);
+template hipError_t launch_block6_init<double>(const Block6Args<double>&, hipStream_t);
+template hipError_t launch_block6_step<float>(const Block6Args<float>&, hipStream_t);
+template hipError_t launch_block6_step<double>(const Block6Args<double>&, hipStream_t);
+template hipError_t launch_block6_sync<float>(float*, float*, const float*, const float*, const float*, const float*, const float*, const float*, const unsigned long long*,
+                                              const BlockStatus*, unsigned, const BlockParams&, hipStream_t);
+template hipError_t launch_block6_sync<double>(double*, double*, const double*, const double*, const double*, const double*, const double*, const double*,
+                                               const unsigned long long*, const BlockStatus*, unsigned, const BlockParams&, hipStream_t);
+
+}  // namespace nb

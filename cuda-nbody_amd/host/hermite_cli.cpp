@@ -1,8 +1,9 @@
-// hermite_cli.cpp -- `nbody --integrator=hermite`, `hermite6` and `hermite-block` (hermite_cli.hpp)
+// hermite_cli.cpp -- `nbody --integrator=hermite`, `hermite6`, `hermite-block` and `hermite6-block` (hermite_cli.hpp)
 #include "hermite_cli.hpp"
 
 #include "bodysystemhip_hermite.hpp"
 #include "bodysystemhip_hermite6.hpp"
+#include "bodysystemhip_hermite6_block.hpp"
 #include "bodysystemhip_hermite_block.hpp"
 #include "compute.hpp"
 #include "field_cli.hpp"
@@ -67,16 +68,32 @@ template <typename T> auto write_dump(const HermiteRun& run, const std::vector<T
     out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
 }
 
-// --integrator=hermite-block: dt_max = dt, --steps=K advances to K dt, --benchmark times `iterations` intervals of dt after one untimed;
-// interactions are counted as the status record counts them: sum of n_act * N
-template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
+// what --benchmark prints of a scheme: its name, the flops of one interaction as its library evaluates it, and what the interaction returns
+struct Scheme {
+    const char* name;
+    int         flops;
+    const char* interaction;
+};
+// an acceleration + jerk interaction: 3 + 3 subtractions, 2 x 5 for r.r + eps^2 and r.w, rsqrt (4, the reference's convention), 2 + 1
+// products for s^-2, s^-3 and the mass, 2 for -3 (r.w) s^-2, 6 + 12 for the two sums
+constexpr Scheme kHermite4{"hermite", 43, "acceleration + jerk"};
+// an acceleration + jerk + snap interaction, counted the same way: 9 subtractions, 5 + 5 + 11 for r.r + eps^2, r.w and w.w + r.b, rsqrt (4),
+// 2 + 1 products for s^-2, s^-3 and the mass, 7 for alpha, beta and their multiples by -3 and -6, 6 + 12 + 18 for the three sums
+constexpr Scheme kHermite6{"hermite6", 80, "acceleration + jerk + snap"};
+// the block integrators: hermite-block prints no FLOP line (its output is what it was); hermite6-block counts hermite6's interaction
+constexpr Scheme kHermiteBlock{"hermite-block", 0, "acceleration + jerk"};
+constexpr Scheme kHermite6Block{"hermite6-block", kHermite6.flops, kHermite6.interaction};
+
+// --integrator=hermite-block and hermite6-block: dt_max = dt, --steps=K advances to K dt, --benchmark times `iterations` intervals of dt after
+// one untimed; interactions are counted as the status record counts them: sum of n_act * N
+template <typename T, typename System> auto run_block_typed(const HermiteRun& run, const Scheme& scheme) -> void {
     const auto     n = run.num_bodies;
     std::vector<T> pos(4 * n), vel(4 * n);
     startup_state<T>(run, pos, vel);
     const double dt_max = static_cast<double>(static_cast<T>(run.params.time_step));
     const T      softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
     const auto   params = nb_hermite_block_params_t{run.eta, 0.01, dt_max, run.levels, 0};
-    auto         system = BodySystemHIPHermiteBlock<T>(n, softening_sq, params);
+    auto         system = System(n, softening_sq, params);
     system.set_state(pos, vel);
     const auto measure = run.energy && (run.benchmark || run.steps > 0);
     nb_energy_t start{};
@@ -126,10 +143,15 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
         stop.synchronize();
         const float  milliseconds = HipEvent::elapsed_ms(begin, stop);
         const double interactions = static_cast<double>(end.body_steps - warm.body_steps) * static_cast<double>(n);
-        std::printf("%zu bodies, hermite-block integrator, total time for %d intervals of dt_max: %s ms\n", n, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("%zu bodies, %s integrator, total time for %d intervals of dt_max: %s ms\n", n, scheme.name, run.iterations, text::width3(milliseconds).c_str());
         std::printf("= %s ms per interval\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
         report("= ", warm, end);
-        std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
+        const auto per_second = static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3));
+        std::printf("= %s billion interactions per second\n", text::width3(per_second).c_str());
+        if (scheme.flops > 0) {
+            std::printf("= %s %s-precision GFLOP/s at %d flops per %s interaction\n", text::width3(per_second * static_cast<float>(scheme.flops)).c_str(),
+                        sizeof(T) == 8 ? "double" : "single", scheme.flops, scheme.interaction);
+        }
         report_energy(1 + static_cast<std::size_t>(run.iterations));
         report_neighbourhood();
         report_field_points();
@@ -149,19 +171,6 @@ template <typename T> auto run_block_typed(const HermiteRun& run) -> void {
     report_structure();
     report_field_points();
 }
-
-// what --benchmark prints of a scheme: its name, the flops of one interaction as its library evaluates it, and what the interaction returns
-struct Scheme {
-    const char* name;
-    int         flops;
-    const char* interaction;
-};
-// an acceleration + jerk interaction: 3 + 3 subtractions, 2 x 5 for r.r + eps^2 and r.w, rsqrt (4, the reference's convention), 2 + 1
-// products for s^-2, s^-3 and the mass, 2 for -3 (r.w) s^-2, 6 + 12 for the two sums
-constexpr Scheme kHermite4{"hermite", 43, "acceleration + jerk"};
-// an acceleration + jerk + snap interaction, counted the same way: 9 subtractions, 5 + 5 + 11 for r.r + eps^2, r.w and w.w + r.b, rsqrt (4),
-// 2 + 1 products for s^-2, s^-3 and the mass, 7 for alpha, beta and their multiples by -3 and -6, 6 + 12 + 18 for the three sums
-constexpr Scheme kHermite6{"hermite6", 80, "acceleration + jerk + snap"};
 
 template <typename T, typename System> auto run_typed(const HermiteRun& run, const Scheme& scheme) -> void {
     const auto     n = run.num_bodies;
@@ -235,7 +244,11 @@ template <typename T, typename System> auto run_typed(const HermiteRun& run, con
 
 auto run_hermite(const HermiteRun& run) -> void {
     if (run.block) {
-        if (run.fp64) run_block_typed<double>(run); else run_block_typed<float>(run);
+        if (run.sixth) {
+            if (run.fp64) run_block_typed<double, BodySystemHIPHermite6Block<double>>(run, kHermite6Block); else run_block_typed<float, BodySystemHIPHermite6Block<float>>(run, kHermite6Block);
+            return;
+        }
+        if (run.fp64) run_block_typed<double, BodySystemHIPHermiteBlock<double>>(run, kHermiteBlock); else run_block_typed<float, BodySystemHIPHermiteBlock<float>>(run, kHermiteBlock);
         return;
     }
     if (run.sixth) {

@@ -1,6 +1,7 @@
 // hermite_cli.hpp -- `nbody --integrator=hermite`: the single-system run stepped by the 4th-order Hermite scheme (BodySystemHIPHermite),
 // `nbody --integrator=hermite6`: the same run stepped by the 6th-order scheme (BodySystemHIPHermite6), and
-// `nbody --integrator=hermite-block`: the 4th-order run with block time steps (BodySystemHIPHermiteBlock).
+// `nbody --integrator=hermite-block`: the 4th-order run with block time steps (BodySystemHIPHermiteBlock), and
+// `nbody --integrator=hermite6-block`: the 6th-order run with block time steps (BodySystemHIPHermite6Block).
 #pragma once
 
 #include "nbody_types.hpp"
@@ -22,9 +23,9 @@ struct HermiteRun {
     unsigned              knn = 0;  // --knn=<K> (0: not asked for): report_knn of the final state
     double                neighbours = -1.0;  // --neighbours=<radius> (< 0: not asked for): report_neighbours of the final state
     std::vector<double>   field_points;  // --field=<file>: x y z of every point (empty: not asked for): report_field of the final state
-    bool                  sixth = false;  // --integrator=hermite6: the 6th-order scheme (never with `block`)
+    bool                  sixth = false;  // --integrator=hermite6: the 6th-order scheme; with `block`: --integrator=hermite6-block
     bool                  block = false;  // --integrator=hermite-block: dt_max = the demo row's dt, `steps` / `iterations` count intervals of dt_max
-    double                eta = 0.02;     // --eta (the first steps use eta_start = 0.01)
+    double                eta = 0.02;     // --eta (the first steps use eta_start = 0.01); hermite6-block: 0.2 unless given
     int                   levels = 30;    // --levels: steps down to dt_max * 2^-levels
 };
 

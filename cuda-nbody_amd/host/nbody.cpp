@@ -11,6 +11,7 @@
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 //                     --integrator=hermite6 (6th-order Hermite steps: libnbody_hip_hermite6.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
+//                     --integrator=hermite6-block (6th-order Hermite steps with block time steps: libnbody_hip_hermite6_block.so)
 //                     --integrator=hermite-ensemble --systems=<B> (... of B systems, a time step per system: libnbody_hip_hermite_ensemble.so)
 //                     --integrator=hermite-block-ensemble --systems=<B> (block time steps of B systems: libnbody_hip_hermite_block_ensemble.so)
 #include "ensemble_cli.hpp"
@@ -83,6 +84,7 @@ struct Options {
     bool                  hermite = false;  // --integrator=hermite or hermite-block (euler, the reference's step, is the default)
     bool                  hermite_block = false;  // --integrator=hermite-block
     bool                  hermite6 = false;  // --integrator=hermite6 (`hermite` is set too: its restrictions and messages apply)
+    bool                  hermite6_block = false;  // --integrator=hermite6-block (`hermite` and `hermite_block` are set too: their restrictions, options and messages apply)
     bool                  hermite_ensemble = false;  // --integrator=hermite-ensemble (with --systems)
     bool                  hermite_block_ensemble = false;  // --integrator=hermite-block-ensemble (with --systems)
     std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble, hermite-block-ensemble)
@@ -144,6 +146,9 @@ Options:
   --levels UINT [30]          hermite-block: the deepest level, 0 to 40 (time steps down to dt * 2^-levels)
   --integrator=hermite6       hermite's run and restrictions with the 6th-order scheme: acceleration, jerk and snap per interaction, the
                               global error falls with dt^6
+  --integrator=hermite6-block  hermite-block's run, restrictions, --eta and --levels with the 6th-order scheme.  --eta [0.2]: it sits
+                              inside the root of the step criterion as in hermite-block, and 0.2 here does what 0.02 does there, with a
+                              quarter of the block steps
   --integrator=hermite-ensemble  with --systems (required; its restrictions apply, numbodies * systems at most 2^28): Hermite steps of every
                               system in one launch per stage.  --steps=K takes K steps of --integrator=hermite's dt, --dump writes in
                               --systems' format, --benchmark counts B*N^2 acceleration + jerk interactions per step
@@ -294,10 +299,12 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
         } else if (name == "integrator") {
             const auto v = take_value();
-            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite6" || *v == "hermite-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble");
+            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite6" || *v == "hermite-block" || *v == "hermite6-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble");
             if (ok) {
                 options.hermite_ensemble = *v == "hermite-ensemble", options.hermite_block_ensemble = *v == "hermite-block-ensemble";
-                options.hermite = (*v == "hermite" || *v == "hermite6" || *v == "hermite-block"), options.hermite_block = *v == "hermite-block", options.hermite6 = *v == "hermite6";
+                options.hermite6_block = *v == "hermite6-block";
+                options.hermite = (*v == "hermite" || *v == "hermite6" || *v == "hermite-block" || options.hermite6_block);
+                options.hermite_block = (*v == "hermite-block" || options.hermite6_block), options.hermite6 = *v == "hermite6";
             }
         } else if (name == "eta") {
             const auto v = take_value();
@@ -495,8 +502,8 @@ auto main(int argc, char** argv) -> int {
             run.knn        = cmd_options.knn.value_or(0u);
             run.field_points = cmd_options.field_points;
             run.block      = cmd_options.hermite_block;
-            run.sixth      = cmd_options.hermite6;
-            run.eta        = cmd_options.eta.value_or(run.eta);
+            run.sixth      = cmd_options.hermite6 || cmd_options.hermite6_block;
+            run.eta        = cmd_options.eta.value_or(cmd_options.hermite6_block ? 0.2 : run.eta);
             run.levels     = cmd_options.levels.value_or(run.levels);
             run_hermite(run);
             return 0;
