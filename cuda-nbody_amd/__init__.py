@@ -48,6 +48,9 @@ HERMITE_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_ENSEMBLE_LIB", os.
 HERMITE_BLOCK_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE_BLOCK_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite_block_ensemble.so"))
 # 6th-order Hermite steps with block time steps (include/nbody_hip_hermite6_block.h) are a twelfth, loaded by hermite6_block_lib().
 HERMITE6_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_BLOCK_LIB", os.path.join(HERE, "libnbody_hip_hermite6_block.so"))
+# 6th-order Hermite steps of many independent systems, a time step per system (include/nbody_hip_hermite6_ensemble.h) are a thirteenth,
+# loaded by hermite6_ensemble_lib().
+HERMITE6_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite6_ensemble.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -471,6 +474,34 @@ HERMITE_ENSEMBLE_SIGNATURES = {
 }
 
 # include/nbody_hip_hermite_block_ensemble.h: exported by libnbody_hip_hermite_block_ensemble.so, and nothing else is
+# include/nbody_hip_hermite6_ensemble.h: exported by libnbody_hip_hermite6_ensemble.so, and nothing else is.  Plan, clock, status, flags and
+# limits are nbody_hip_hermite_ensemble.h's.
+HERMITE6_ENSEMBLE_SIGNATURES = {
+    "nb_hermite6_ensemble_workspace_bytes": (_ci, [_cu, _cu, _cu, _P(_sz)]),
+    "nb_hermite6_ensemble_plan_f32": (_ci, [_cu, _cu, _P(HermiteEnsemblePlan)]),
+    "nb_hermite6_ensemble_plan_f64": (_ci, [_cu, _cu, _P(HermiteEnsemblePlan)]),
+    # acc_out, jerk_out, snap_out, positions, velocities, acc_in, workspace, bytes, N, B, softening_sq, system_softening_sq, stream
+    "nb_hermite6_ensemble_eval_f32": (_ci, [_vp] * 7 + [_sz, _cu, _cu, _cf, _vp, _vp]),
+    "nb_hermite6_ensemble_eval_f64": (_ci, [_vp] * 7 + [_sz, _cu, _cu, _cd, _vp, _vp]),
+    # accelerations, jerks, snaps, crackles, positions, velocities, workspace, bytes, N, B, softening_sq, system_softening_sq, stream
+    "nb_hermite6_ensemble_init_f32": (_ci, [_vp] * 7 + [_sz, _cu, _cu, _cf, _vp, _vp]),
+    "nb_hermite6_ensemble_init_f64": (_ci, [_vp] * 7 + [_sz, _cu, _cu, _cd, _vp, _vp]),
+    # new_pos, old_pos, vel, acc, jerk, snap, crackle, workspace, bytes, N, B, delta_time, softening_sq, system_params, stream
+    "nb_hermite6_ensemble_step_f32": (_ci, [_vp] * 8 + [_sz, _cu, _cu, _cf, _cf, _vp, _vp]),
+    "nb_hermite6_ensemble_step_f64": (_ci, [_vp] * 8 + [_sz, _cu, _cu, _cd, _cd, _vp, _vp]),
+    # acc, jerk, snap, crackle, N, B, eta, dt_out, workspace, bytes, stream
+    "nb_hermite6_ensemble_timestep_f32": (_ci, [_vp] * 4 + [_cu, _cu, _cf, _vp, _vp, _sz, _vp]),
+    "nb_hermite6_ensemble_timestep_f64": (_ci, [_vp] * 4 + [_cu, _cu, _cd, _vp, _vp, _sz, _vp]),
+    # acc, jerk, snap, crackle, pos, vel, clocks, N, B, softening_sq, system_softening_sq, eta, workspace, bytes, stream
+    "nb_hermite6_ensemble_begin_f32": (_ci, [_vp] * 7 + [_cu, _cu, _cf, _vp, _cf, _vp, _sz, _vp]),
+    "nb_hermite6_ensemble_begin_f64": (_ci, [_vp] * 7 + [_cu, _cu, _cd, _vp, _cd, _vp, _sz, _vp]),
+    # new_pos, old_pos, vel, acc, jerk, snap, crackle, clocks, status, workspace, bytes, N, B, t_stop, dt_max, eta, softening_sq,
+    # system_softening_sq, stream
+    "nb_hermite6_ensemble_advance_f32": (_ci, [_vp] * 10 + [_sz, _cu, _cu, _cd, _cd, _cf, _cf, _vp, _vp]),
+    "nb_hermite6_ensemble_advance_f64": (_ci, [_vp] * 10 + [_sz, _cu, _cu, _cd, _cd, _cd, _cd, _vp, _vp]),
+}
+
+
 class HermiteBlockEnsemblePlan(ctypes.Structure):
     """nb_hermite_block_ensemble_plan_t: nb_hermite_block_plan_t of (N, n_act), and what the number of systems adds"""
     _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("unroll", _ci), ("tiles", _cu), ("ranges", _cu), ("groups", _cu),
@@ -561,6 +592,11 @@ def hermite6_lib() -> ctypes.CDLL:
 def hermite_ensemble_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
     return _load(HERMITE_ENSEMBLE_LIB_PATH, HERMITE_ENSEMBLE_SIGNATURES)
+
+
+def hermite6_ensemble_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite6_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    return _load(HERMITE6_ENSEMBLE_LIB_PATH, HERMITE6_ENSEMBLE_SIGNATURES)
 
 
 def hermite_block_ensemble_lib() -> ctypes.CDLL:
@@ -1103,11 +1139,12 @@ class HermiteEnsemble(_HermiteState):
     ``status()`` read the device records.  `softening_sq`: a scalar or one value per system."""
 
     _library, _prefix = staticmethod(hermite_ensemble_lib), "nb_hermite_ensemble_"
+    _query = staticmethod(hermite_ensemble_workspace_bytes)
 
     def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, softening_sq=None):
-        super().__init__(dtype)
+        _DeviceState.__init__(self, dtype)
         self.num_bodies, self.num_systems = int(num_bodies), int(num_systems)
-        self._workspace_bytes = hermite_ensemble_workspace_bytes(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
+        self._workspace_bytes = self._query(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
         self.shape = (self.num_systems, self.num_bodies, 4)
         nbytes = 4 * self.num_bodies * self.num_systems * self.dtype.itemsize
         self._pos, self._vel, self._acc, self._jerk = (DeviceBuffer(nbytes) for _ in range(4))
@@ -1123,22 +1160,30 @@ class HermiteEnsemble(_HermiteState):
         return [b for b in (self._pos, self._vel, self._acc, self._jerk, self._workspace, self._clocks, self._status, self._per_system, self._params, self._system_eps2)
                 if b is not None]
 
+    def _derivatives(self):
+        return self._acc.ptr, self._jerk.ptr
+
+    def _step_table(self, delta_time):
+        """the {dt, softening^2, -, -} table of a step with a dt or a softening^2 per system, uploaded; None where the scalars do"""
+        if np.ndim(delta_time) == 0 and self._system_eps2 is None:
+            return None
+        table = np.zeros((self.num_systems, 4), self.dtype)
+        table[:, 0], table[:, 1] = delta_time, self.softening_sq
+        self._params.upload(table)
+        return table
+
     def eval(self, stream=None) -> None:
         self._call("eval", self._acc.ptr, self._jerk.ptr, self._pos.ptr, self._vel.ptr, self.num_bodies, self.num_systems, *self._softening(), stream)
 
     def step(self, delta_time, stream=None) -> None:
         """One step of every system: `delta_time` a scalar, or one dt per system (uploaded first, with the systems' softening^2)."""
-        table = None
-        if np.ndim(delta_time) != 0 or self._system_eps2 is not None:
-            table = np.zeros((self.num_systems, 4), self.dtype)
-            table[:, 0], table[:, 1] = delta_time, self.softening_sq
-            self._params.upload(table)
+        table = self._step_table(delta_time)
         self._call("step", self._pos.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies,
                    self.num_systems, self._scalar(0 if table is not None else delta_time), self._scalar(self.softening_sq[0]),
                    self._params.ptr if table is not None else None, stream)
 
     def suggested_dt(self, eta, stream=None) -> np.ndarray:
-        self._call("timestep", self._acc.ptr, self._jerk.ptr, self.num_bodies, self.num_systems, self._scalar(eta), self._per_system.ptr, self._workspace.ptr,
+        self._call("timestep", *self._derivatives(), self.num_bodies, self.num_systems, self._scalar(eta), self._per_system.ptr, self._workspace.ptr,
                    self._workspace_bytes, stream)
         out = np.empty(self.num_systems, dtype=self.dtype)
         check(lib().nb_d2h(out.ctypes.data_as(_vp), self._per_system.ptr, out.nbytes, stream), "nb_d2h")
@@ -1162,6 +1207,65 @@ class HermiteEnsemble(_HermiteState):
         """the status record of the last advance"""
         raw = self._status.download(np.empty(ctypes.sizeof(HermiteEnsembleStatus), dtype=np.uint8))
         return HermiteEnsembleStatus.from_buffer_copy(raw.tobytes())
+
+
+def hermite6_ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> HermiteEnsemblePlan:
+    """nb_hermite6_ensemble_plan_*: the geometry of `num_systems` systems of `num_bodies` bodies"""
+    return _plan(hermite6_ensemble_lib, "hermite6_ensemble", HermiteEnsemblePlan, dtype, num_bodies, num_systems)
+
+
+def hermite6_ensemble_workspace_bytes(num_bodies: int, num_systems: int, dtype=np.float32) -> int:
+    return _query_workspace_bytes(hermite6_ensemble_lib, "hermite6_ensemble", dtype, num_bodies, num_systems)
+
+
+class Hermite6Ensemble(HermiteEnsemble):
+    """B independent systems of N bodies on the device, stepped together by the 6th-order Hermite scheme of
+    include/nbody_hip_hermite6_ensemble.h.
+
+    HermiteEnsemble's arrays and methods plus the snaps and crackles.  ``eval`` is nb_hermite6_ensemble_init_*: it fills the stored
+    accelerations, jerks and snaps and zeroes the crackles (what starts a fixed-dt run); ``suggested_dt(eta)`` reads Aarseth's
+    eta sqrt(min (|a||s| + |j|^2) / (|j||c| + |s|^2)) of every system back; ``begin`` / ``advance`` are the adaptive form with that step."""
+
+    _library, _prefix = staticmethod(hermite6_ensemble_lib), "nb_hermite6_ensemble_"
+    _query = staticmethod(hermite6_ensemble_workspace_bytes)
+
+    def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, softening_sq=None):
+        super().__init__(num_bodies, num_systems, dtype, softening_sq)
+        nbytes = 4 * self.num_bodies * self.num_systems * self.dtype.itemsize
+        self._snap, self._crackle = DeviceBuffer(nbytes), DeviceBuffer(nbytes)
+
+    def _buffers(self):
+        return super()._buffers() + [b for b in (getattr(self, "_snap", None), getattr(self, "_crackle", None)) if b is not None]
+
+    def _derivatives(self):
+        return self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr
+
+    def eval(self, stream=None) -> None:
+        self._call("init", *self._derivatives(), self._pos.ptr, self._vel.ptr, self._workspace.ptr, self._workspace_bytes, self.num_bodies, self.num_systems,
+                   *self._softening(), stream)
+
+    def step(self, delta_time, stream=None) -> None:
+        """One step of every system: `delta_time` a scalar, or one dt per system (uploaded first, with the systems' softening^2)."""
+        table = self._step_table(delta_time)
+        self._call("step", self._pos.ptr, self._pos.ptr, self._vel.ptr, *self._derivatives(), self._workspace.ptr, self._workspace_bytes, self.num_bodies,
+                   self.num_systems, self._scalar(0 if table is not None else delta_time), self._scalar(self.softening_sq[0]),
+                   self._params.ptr if table is not None else None, stream)
+
+    def begin(self, eta, stream=None) -> None:
+        self._call("begin", *self._derivatives(), self._pos.ptr, self._vel.ptr, self._clocks.ptr, self.num_bodies, self.num_systems, *self._softening(),
+                   self._scalar(eta), self._workspace.ptr, self._workspace_bytes, stream)
+
+    def advance(self, t_stop, eta, dt_max=float("inf"), calls: int = 1, stream=None) -> None:
+        """`calls` calls of nb_hermite6_ensemble_advance_*: every system that can still move takes `calls` steps towards t_stop; nothing is read back."""
+        for _ in range(calls):
+            self._call("advance", self._pos.ptr, self._pos.ptr, self._vel.ptr, *self._derivatives(), self._clocks.ptr, self._status.ptr, self._workspace.ptr,
+                       self._workspace_bytes, self.num_bodies, self.num_systems, float(t_stop), float(dt_max), self._scalar(eta), *self._softening(), stream)
+
+    def get_snaps(self) -> np.ndarray:
+        return self._download(self._snap)
+
+    def get_crackles(self) -> np.ndarray:
+        return self._download(self._crackle)
 
 
 def hermite_block_plan(num_bodies: int, num_active: int, dtype=np.float32) -> HermiteBlockPlan:

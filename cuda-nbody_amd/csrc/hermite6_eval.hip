@@ -18,6 +18,8 @@ namespace {
 
 #include "hermite_powers.h"
 
+#include "hermite6_ratio.h"
+
 template <typename T> struct BodyJ {
     typename Lane<T>::raw4 p, v, a;  // {x, y, z, m}, {vx, vy, vz, -}, {ax, ay, az, -} in scalar registers
 };
@@ -87,33 +89,9 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
         j1.x = LT::get(second[3], k) * out_scale, j1.y = LT::get(second[4], k) * out_scale, j1.z = LT::get(second[5], k) * out_scale, j1.w = 0;
         s1.x = LT::get(second[6], k) * out_scale, s1.y = LT::get(second[7], k) * out_scale, s1.z = LT::get(second[8], k) * out_scale, s1.w = 0;
         if constexpr (STEP) {
-            // v1 = v + (a0 + a1) h/2 - (j1 - j0) h^2/10 + (s0 + s1) h^3/120,   x1 = x + (v + v1) h/2 - (a1 - a0) h^2/10 + (j0 + j1) h^3/120
-            // c1, the third derivative at the step's end of the quintic through (a, j, s) at both ends:
-            //   D0 = a1 - a0 - j0 h - s0 h^2/2,  D1 = (j1 - j0 - s0 h) h,  D2 = (s1 - s0) h^2,  c1 = (60 D0 - 36 D1 + 9 D2) / h^3
-            // (the small terms are summed first: v1 and x1 then take one rounding of their own size, like a plain v + increment)
-            const T    h = e.dt, h2 = h * T(0.5), hh = h * h, t10 = hh * T(0.1), h3 = hh * h, t120 = h3 * (T(1) / T(120));
-            const vec4 x  = reinterpret_cast<const vec4*>(e.old_pos)[i];
-            vec4       v  = reinterpret_cast<const vec4*>(e.vel)[i];
-            const vec4 a0 = reinterpret_cast<const vec4*>(e.acc)[i];
-            const vec4 j0 = reinterpret_cast<const vec4*>(e.jerk)[i];
-            const vec4 s0 = reinterpret_cast<const vec4*>(e.snap)[i];
-            vec4       x1, c1;
-            auto       component = [&](T xq, T& vq, T a0q, T j0q, T s0q, T a1q, T j1q, T s1q, T& x1q, T& c1q) {
-                const T v1 = vq + __builtin_fma(h2, a0q + a1q, __builtin_fma(t120, s0q + s1q, -t10 * (j1q - j0q)));
-                x1q        = xq + __builtin_fma(h2, vq + v1, __builtin_fma(t120, j0q + j1q, -t10 * (a1q - a0q)));
-                const T d0 = __builtin_fma(-h2 * h, s0q, __builtin_fma(-h, j0q, a1q - a0q));
-                const T d1 = __builtin_fma(-h, s0q, j1q - j0q) * h;
-                const T d2 = (s1q - s0q) * hh;
-                c1q        = __builtin_fma(T(9), d2, __builtin_fma(T(-36), d1, T(60) * d0)) / h3;
-                vq         = v1;
-            };
-            component(x.x, v.x, a0.x, j0.x, s0.x, a1.x, j1.x, s1.x, x1.x, c1.x);
-            component(x.y, v.y, a0.y, j0.y, s0.y, a1.y, j1.y, s1.y, x1.y, c1.y);
-            component(x.z, v.z, a0.z, j0.z, s0.z, a1.z, j1.z, s1.z, x1.z, c1.z);
-            x1.w = x.w, c1.w = 0;
-            reinterpret_cast<vec4*>(e.new_pos)[i] = x1;
-            reinterpret_cast<vec4*>(e.vel)[i]     = v;
-            reinterpret_cast<vec4*>(e.crackle)[i] = c1;
+#define HERMITE6_STEP_DT e.dt
+#define HERMITE6_STORED(array) e.array
+#include "hermite6_correct.inc"
         }
         reinterpret_cast<vec4*>(e.acc)[i]  = a1;
         reinterpret_cast<vec4*>(e.jerk)[i] = j1;
@@ -126,21 +104,10 @@ template <typename T> __global__ __launch_bounds__(256) void hermite6_pack(T* st
     using vec4       = typename Lane<T>::vec4;
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const vec4 p = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i];
-    T          bx = 0, by = 0, bz = 0;
-    if (acc_in) {
-        const vec4 b = reinterpret_cast<const vec4*>(acc_in)[i];
-        bx = b.x, by = b.y, bz = b.z;
-    }
-    vec4* const out = reinterpret_cast<vec4*>(state12) + 3 * static_cast<size_t>(i);
-    out[0] = p;
-    out[1] = vec4{v.x, v.y, v.z, 0};
-    out[2] = vec4{bx, by, bz, 0};
-    if (zero) reinterpret_cast<vec4*>(zero)[i] = vec4{0, 0, 0, 0};
+#include "hermite6_pack.inc"
 }
 
 // The predictor -> state12 {x_p, m, v_p, 0, a_p, 0}, Horner in dt.  HBM-bound.
-//   x_p = x + v h + a h^2/2 + j h^3/6 + s h^4/24 + c h^5/120,   v_p = v + a h + j h^2/2 + s h^3/6 + c h^4/24,   a_p = a + j h + s h^2/2 + c h^3/6
 template <typename T>
 __global__ __launch_bounds__(256) void hermite6_predict(const T* pos, const T* vel, const T* acc, const T* jerk, const T* snap, const T* crackle, T* state12, unsigned n, T dt) {
     using vec4       = typename Lane<T>::vec4;
@@ -148,35 +115,10 @@ __global__ __launch_bounds__(256) void hermite6_predict(const T* pos, const T* v
     if (i >= n) return;
     const vec4 x = reinterpret_cast<const vec4*>(pos)[i], v = reinterpret_cast<const vec4*>(vel)[i], a = reinterpret_cast<const vec4*>(acc)[i];
     const vec4 j = reinterpret_cast<const vec4*>(jerk)[i], s = reinterpret_cast<const vec4*>(snap)[i], c = reinterpret_cast<const vec4*>(crackle)[i];
-    const T    h2 = dt * T(0.5), h3 = dt * (T(1) / T(3)), h4 = dt * T(0.25), h5 = dt * T(0.2);
-    vec4       xp, vp, ap;
-    auto       component = [&](T xq, T vq, T aq, T jq, T sq, T cq, T& xpq, T& vpq, T& apq) {
-        xpq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, __builtin_fma(h4, __builtin_fma(h5, cq, sq), jq), aq), vq), xq);
-        vpq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, __builtin_fma(h4, cq, sq), jq), aq), vq);
-        apq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, cq, sq), jq), aq);
-    };
-    component(x.x, v.x, a.x, j.x, s.x, c.x, xp.x, vp.x, ap.x);
-    component(x.y, v.y, a.y, j.y, s.y, c.y, xp.y, vp.y, ap.y);
-    component(x.z, v.z, a.z, j.z, s.z, c.z, xp.z, vp.z, ap.z);
-    xp.w = x.w, vp.w = 0, ap.w = 0;
+#include "hermite6_predict.inc"
     reinterpret_cast<vec4*>(state12)[3 * static_cast<size_t>(i)]     = xp;
     reinterpret_cast<vec4*>(state12)[3 * static_cast<size_t>(i) + 1] = vp;
     reinterpret_cast<vec4*>(state12)[3 * static_cast<size_t>(i) + 2] = ap;
-}
-
-// (|a||s| + |j|^2) / (|j||c| + |s|^2) of one body, in fp64 for either precision; +inf where the denominator is not positive or the
-// ratio not finite
-template <typename T> __device__ __forceinline__ double aarseth_ratio(const typename Lane<T>::vec4& a, const typename Lane<T>::vec4& j, const typename Lane<T>::vec4& s,
-                                                                    const typename Lane<T>::vec4& c) {
-    const auto norm2 = [](const typename Lane<T>::vec4& q) {
-        const double x = q.x, y = q.y, z = q.z;
-        return x * x + y * y + z * z;
-    };
-    const double a2 = norm2(a), j2 = norm2(j), s2 = norm2(s), c2 = norm2(c);
-    const double num = __builtin_sqrt(a2 * s2) + j2, den = __builtin_sqrt(j2 * c2) + s2;
-    if (!(den > 0)) return __builtin_inf();
-    const double q = num / den;
-    return (q == q && q - q == 0) ? q : __builtin_inf();
 }
 
 __device__ __forceinline__ double block_min(double m, double* lds) {

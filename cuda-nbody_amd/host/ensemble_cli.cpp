@@ -3,6 +3,7 @@
 
 #include "bodyensemblehip.hpp"
 #include "bodyensemblehip_hermite.hpp"
+#include "bodyensemblehip_hermite6.hpp"
 #include "bodyensemblehip_hermite_block.hpp"
 #include "compute.hpp"
 #include "randomise_bodies.hpp"
@@ -24,13 +25,15 @@ template <typename T> auto write_dump(const EnsembleRun& run, const std::vector<
 }
 
 // --integrator=hermite-ensemble: --steps=K takes K fixed steps of --integrator=hermite's dt; --t-end runs the adaptive form, batches of calls
-// between reads of the 64-byte status record; --benchmark times `iterations` fixed steps after one untimed, B N^2 interactions per step
-template <typename T> auto run_hermite_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+// between reads of the 64-byte status record; --benchmark times `iterations` fixed steps after one untimed, B N^2 interactions per step.
+// --integrator=hermite6-ensemble is the same run on BodyEnsembleHIPHermite6, with --integrator=hermite6's name and interaction count.
+template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+    const char* const name = run.sixth ? "hermite6" : "hermite";
     const auto n = run.num_bodies, b = run.num_systems;
     // BodySystemHIP's conversions: dt float -> T, softening^2 = T(s) * T(s)
     const T dt = static_cast<T>(run.params.time_step);
     const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
-    auto ensemble = BodyEnsembleHIPHermite<T>(n, b, softening_sq);
+    auto ensemble = Ensemble(n, b, softening_sq);
     ensemble.set_state(pos, vel);
     if (run.benchmark) {
         ensemble.update(dt);  // (untimed, as Compute::run_benchmark)
@@ -42,12 +45,12 @@ template <typename T> auto run_hermite_typed(const EnsembleRun& run, std::vector
         const float milliseconds = HipEvent::elapsed_ms(start, stop);
         const float frequency    = static_cast<float>(run.iterations) * (1000.0f / milliseconds);
         const float interactions = static_cast<float>(static_cast<double>(b) * static_cast<double>(n) * static_cast<double>(n) * 1e-9) * frequency;
-        const int   flops        = 43;  // an acceleration + jerk interaction, as --integrator=hermite counts it
-        std::printf("%zu bodies x %zu systems, hermite integrator, total time for %d iterations: %s ms\n", n, b, run.iterations, text::width3(milliseconds).c_str());
+        const int   flops        = run.sixth ? 80 : 43;  // an interaction, as --integrator=hermite6 / hermite counts it
+        std::printf("%zu bodies x %zu systems, %s integrator, total time for %d iterations: %s ms\n", n, b, name, run.iterations, text::width3(milliseconds).c_str());
         std::printf("= %s ms per step\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
         std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
-        std::printf("= %s %s-precision GFLOP/s at %d flops per acceleration + jerk interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
-                    sizeof(T) == 8 ? "double" : "single", flops);
+        std::printf("= %s %s-precision GFLOP/s at %d flops per %s interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
+                    sizeof(T) == 8 ? "double" : "single", flops, run.sixth ? "acceleration + jerk + snap" : "acceleration + jerk");
         return;
     }
     if (run.t_end > 0.0) {
@@ -62,7 +65,7 @@ template <typename T> auto run_hermite_typed(const EnsembleRun& run, std::vector
         auto steps = std::vector<unsigned>();
         for (const auto& clock : ensemble.clocks()) steps.push_back(clock.steps);
         std::sort(steps.begin(), steps.end());
-        std::printf("%zu bodies x %zu systems, hermite integrator, eta %g, to t = %g: %u systems done, %u stalled\n", n, b, run.eta, run.t_end, status.done, status.stalled);
+        std::printf("%zu bodies x %zu systems, %s integrator, eta %g, to t = %g: %u systems done, %u stalled\n", n, b, name, run.eta, run.t_end, status.done, status.stalled);
         std::printf("steps per system: fewest %u, median %u, most %u; %llu in all\n", steps.front(), steps[steps.size() / 2], steps.back(), static_cast<unsigned long long>(status.total_steps));
     } else {
         for (std::size_t s = 0; s < run.steps; ++s) ensemble.update(dt);
@@ -145,7 +148,7 @@ template <typename T> auto run_typed(const EnsembleRun& run) -> void {
         return;
     }
     if (run.hermite) {
-        run_hermite_typed<T>(run, pos, vel);
+        if (run.sixth) run_hermite_typed<T, BodyEnsembleHIPHermite6<T>>(run, pos, vel); else run_hermite_typed<T, BodyEnsembleHIPHermite<T>>(run, pos, vel);
         return;
     }
     auto ensemble = BodyEnsembleHIP<T>(n, b, run.mode);

@@ -14,6 +14,7 @@
 //                     --integrator=hermite6-block (6th-order Hermite steps with block time steps: libnbody_hip_hermite6_block.so)
 //                     --integrator=hermite-ensemble --systems=<B> (... of B systems, a time step per system: libnbody_hip_hermite_ensemble.so)
 //                     --integrator=hermite-block-ensemble --systems=<B> (block time steps of B systems: libnbody_hip_hermite_block_ensemble.so)
+//                     --integrator=hermite6-ensemble --systems=<B> (6th-order steps of B systems, a time step per system: libnbody_hip_hermite6_ensemble.so)
 #include "ensemble_cli.hpp"
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
@@ -51,6 +52,10 @@ namespace {
 
 enum class Status { OK = 0, CleanShutDown, InvalidArguments };
 
+// --eta of --integrator=hermite6-ensemble where none is given (the largest of 0.8, 0.4, 0.2, ... that ends 5.7's binary
+// system with at most half the energy error of hermite-ensemble's 0.02, in fewer steps)
+constexpr double kHermite6EnsembleEta = 0.025;
+
 struct Options {
     bool                  fullscreen = false;
     bool                  fp64       = false;
@@ -87,6 +92,7 @@ struct Options {
     bool                  hermite6_block = false;  // --integrator=hermite6-block (`hermite` and `hermite_block` are set too: their restrictions, options and messages apply)
     bool                  hermite_ensemble = false;  // --integrator=hermite-ensemble (with --systems)
     bool                  hermite_block_ensemble = false;  // --integrator=hermite-block-ensemble (with --systems)
+    bool                  hermite6_ensemble = false;  // --integrator=hermite6-ensemble (`hermite_ensemble` is set too: its restrictions, options and messages apply)
     std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble, hermite-block-ensemble)
     std::optional<double> t_end;   // --t-end (hermite-ensemble, hermite-block-ensemble)
     std::optional<int>    levels;  // --levels (hermite-block, hermite-block-ensemble)
@@ -160,6 +166,12 @@ Options:
                               with its own time.  --t-end=T (or --steps=K: T = K * dt) runs every system to its last block step not
                               past T; --dump writes every system synchronised at its own time, in --systems' format; --benchmark
                               times intervals of dt and counts the sum of n_act * N over the systems
+  --integrator=hermite6-ensemble  hermite-ensemble's run, restrictions, --steps, --t-end, --dump and --benchmark with the 6th-order scheme
+                              (acceleration, jerk and snap per interaction).  --eta [0.025]: a system's time step is eta times the ROOT
+                              of the smallest (|a||s| + |j|^2) / (|j||c| + |s|^2) of the system, so eta sits outside the root here;
+                              0.025 ends a cloud with a hard binary with a thirtieth of the energy error of hermite-ensemble's 0.02
+                              in four fifths of its steps, in --fp64; single-precision --t-end runs want --eta=0.2 or more (the
+                              crackle of the step criterion is rounding noise below that, and systems stall)
   --alloc-limit-mib UINT      Test hook (needs LD_PRELOAD=libnbody_hip_lab.so): device allocations above this many MiB are refused
 )";
 
@@ -299,9 +311,11 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
             if (ok) options.mode = (*v == "strict") ? NB_MODE_STRICT : NB_MODE_FAST;
         } else if (name == "integrator") {
             const auto v = take_value();
-            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite6" || *v == "hermite-block" || *v == "hermite6-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble");
+            ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite6" || *v == "hermite-block" || *v == "hermite6-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble" ||
+                            *v == "hermite6-ensemble");
             if (ok) {
-                options.hermite_ensemble = *v == "hermite-ensemble", options.hermite_block_ensemble = *v == "hermite-block-ensemble";
+                options.hermite6_ensemble = *v == "hermite6-ensemble";
+                options.hermite_ensemble = *v == "hermite-ensemble" || options.hermite6_ensemble, options.hermite_block_ensemble = *v == "hermite-block-ensemble";
                 options.hermite6_block = *v == "hermite6-block";
                 options.hermite = (*v == "hermite" || *v == "hermite6" || *v == "hermite-block" || options.hermite6_block);
                 options.hermite_block = (*v == "hermite-block" || options.hermite6_block), options.hermite6 = *v == "hermite6";
@@ -479,7 +493,8 @@ auto main(int argc, char** argv) -> int {
             run.dump        = cmd_options.dump;
             run.hermite     = cmd_options.hermite_ensemble;
             run.t_end       = cmd_options.t_end.value_or(0.0);
-            run.eta         = cmd_options.eta.value_or(run.eta);
+            run.sixth       = cmd_options.hermite6_ensemble;
+            run.eta         = cmd_options.eta.value_or(run.sixth ? kHermite6EnsembleEta : run.eta);
             run.block       = cmd_options.hermite_block_ensemble;
             run.levels      = cmd_options.levels.value_or(run.levels);
             run_ensemble(run);

@@ -71,6 +71,9 @@
  *
  * Limits.  1 <= N <= 2^26 (NB_HERMITE6_MAX_BODIES).  Body indices are 32-bit, byte offsets 64-bit.
  *
+ * Not built here: block time steps are nbody_hip_hermite6_block.h, many small systems in one launch nbody_hip_hermite6_ensemble.h;
+ * block time steps of many systems with this scheme, a pairwise or sharded form and the 8th-order scheme are not built.
+ *
  * Errors.  NB_ERR_INVALID_ARGUMENT, returned before any HIP call, for: a null pointer; N out of range; an array or the workspace
  * not aligned to 4*sizeof(T) (dt_out: sizeof(T), scratch: 8); workspace_bytes / scratch_bytes too small; any two arrays of a call
  * overlapping (but new_positions == old_positions, and acc_out == acc_in).  Otherwise the launch's hipError_t (0 on success).
