@@ -23,11 +23,19 @@ static_assert(nb::kBlockMaxBodies <= nb::kHermite6MaxBodies, "the initial evalua
 
 bool size_ok(unsigned n) { return n >= 1 && n <= nb::kBlockMaxBodies; }
 
-bool params_ok(const nb_hermite_block_params_t* p) {
+// the cube of a step, as the corrector forms it in T (hh = h * h, h3 = hh * h): c1 divides by it
+template <typename T> bool cube_is_normal(double step) {
+    const T h = static_cast<T>(step), hh = h * h, h3 = hh * h;
+    return std::isnormal(h3);
+}
+
+// T: the corrector's precision.  The longest step (dt_max) and the shortest (one tick) must have normal cubes in T.
+template <typename T> bool params_ok(const nb_hermite_block_params_t* p) {
     if (p == nullptr) return false;
     const auto positive = [](double v) { return std::isfinite(v) && v > 0; };
-    return positive(p->eta) && positive(p->eta_start) && positive(p->dt_max) && p->max_level >= 0 && p->max_level <= nb::kBlockMaxLevel &&
-           std::isnormal(std::ldexp(p->dt_max, -p->max_level));
+    if (!(positive(p->eta) && positive(p->eta_start) && positive(p->dt_max) && p->max_level >= 0 && p->max_level <= nb::kBlockMaxLevel)) return false;
+    const double tick = std::ldexp(p->dt_max, -p->max_level);
+    return std::isnormal(tick) && cube_is_normal<T>(tick) && cube_is_normal<T>(p->dt_max);
 }
 
 nb::BlockParams params_of(const nb_hermite_block_params_t* p) { return nb::BlockParams{p->eta, p->eta_start, p->dt_max, p->max_level, 0}; }
@@ -58,7 +66,7 @@ template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_b
 template <typename T>
 bool bind(nb::Block6Args<T>& a, T* pos, T* vel, T* acc, T* jerk, T* snap, T* crackle, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace,
           size_t workspace_bytes, unsigned n, const nb_hermite_block_params_t* params) {
-    if (!size_ok(n) || !params_ok(params)) return false;
+    if (!size_ok(n) || !params_ok<T>(params)) return false;
     const nb::Block6Layout l = nb::block6_layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return false;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
@@ -115,7 +123,7 @@ int step(T* pos, T* vel, T* acc, T* jerk, T* snap, T* crackle, uint64_t* ticks, 
 template <typename T>
 int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const T* snap, const T* crackle, const uint64_t* ticks,
          const nb_hermite_block_status_t* status, unsigned n, const nb_hermite_block_params_t* params, nb_stream_t stream) {
-    if (!size_ok(n) || !params_ok(params)) return NB_ERR_INVALID_ARGUMENT;
+    if (!size_ok(n) || !params_ok<T>(params)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos_out, bodies, al}, {vel_out, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al},
                    {crackle, bodies, al}, {ticks, static_cast<std::uintptr_t>(n) * 8, 8}, {status, 64, 8}})) {

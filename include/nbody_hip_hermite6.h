@@ -52,7 +52,10 @@
  *   crackle   D0 = a1 - a - j h - s h^2/2,  D1 = (j1 - j - s h) h,  D2 = (s1 - s) h^2,   c1 = (60 D0 - 36 D1 + 9 D2) / h^3
  *             (the third derivative, at the step's end, of the quintic through a, j, s at both ends)
  *   store     x1 -> new_positions; v1, a1, j1, s1, c1 in place.
- * There is no damping.  delta_time must not be 0 (c1 divides by h^3).  The bodies j are read from the workspace, so a lane reads
+ * There is no damping.  Range of h: |delta_time|^3, formed in T as (h h) h, must be a normal T (c1 divides by it):
+ * 2^-42 <= |h| <= 2^42 (fp32) / 2^-340 <= |h| <= 2^341 (fp64).  The call does not check it.  Below that range the cube is subnormal and
+ * c1 has no bound, and where it rounds to 0 (|h| <= 2^-50 / 2^-359, and h = 0) c1 is infinite or NaN: the next step's predictor then
+ * makes positions NaN.  Above it h^3 is infinite: v1 and x1 are infinite or NaN.  The bodies j are read from the workspace, so a lane reads
  * and writes its own body's stored state only: new_positions == old_positions IS ALLOWED (and gives the bits of two separate arrays).
  * Every other overlap between the arrays of a call is refused.
  *

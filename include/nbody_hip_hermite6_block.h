@@ -74,6 +74,11 @@
  * overflowed, or the denominator underflowed to 0; init: also where want is 0 -- and for dt_A a finite value that can be too small,
  * down to 0 (the deepest level), where the numerator underflowed over a denominator that did not.
  *
+ * Range of h.  The corrector divides by h^3, formed in T as (h h) h, for every step a body can take, from dt_max down to one tick
+ * q = dt_max 2^-max_level: both cubes must be normal in T -- 2^-42 <= q and dt_max <= 2^42 (fp32) / 2^-340 <= q and dt_max <= 2^341
+ * (fp64) --, and init, step and sync refuse parameters outside that range (fp32: dt_max = 2^-10 with max_level = 33).  Inside it c1 is
+ * held to the evaluation's bounds carried through 60/h^3, 36/h^2 and 9/h, and finite sums give a finite state.
+ *
  * Status.  As nbody_hip_hermite_block.h: now_ticks, block_steps, body_steps = sum of n_act, last_active, deepest_level, flags.
  *
  * Geometry (nb_hermite6_block_plan_*): a function of (N, n_act, precision) alone.  The fields of nb_hermite_block_plan_t with the number
@@ -93,8 +98,8 @@
  *
  * Errors.  NB_ERR_INVALID_ARGUMENT, returned before any HIP call, for: a null pointer; N (or num_active) out of range; an array not
  * aligned to 4*sizeof(T) (ticks, status: 8; levels: 4; workspace: 32); workspace_bytes too small; any two arrays of a call
- * overlapping; a parameter that is not finite and positive, max_level outside [0, 40], a tick that is not a normal double; a NaN
- * t_stop.  Otherwise the launch's hipError_t (0 on success).
+ * overlapping; a parameter that is not finite and positive, max_level outside [0, 40], a tick that is not a normal double, a tick or a
+ * dt_max whose cube is not a normal T ("Range of h"); a NaN t_stop.  Otherwise the launch's hipError_t (0 on success).
  */
 #ifndef NBODY_HIP_HERMITE6_BLOCK_H
 #define NBODY_HIP_HERMITE6_BLOCK_H

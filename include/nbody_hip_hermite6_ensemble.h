@@ -35,7 +35,11 @@
  * either T, and eta sits outside the root.  The formulas, the floor that softening_sq == 0 takes (per system), the predictor, the
  * corrector and the new crackle are those of nbody_hip_hermite6.h, and so are the operand range the error bounds hold on ("Operand
  * range" there; the unit mass a system's unit chunks are recognised by is that system's own first body's) and the range of the time
- * step ("Time step" there).  A dt of 0, scalar or per system, is not allowed (the crackle divides by dt^3), as in that header.
+ * step ("Time step" there).  Range of h: as in that header, |dt|^3 -- scalar or per system -- must be a normal T (the crackle divides
+ * by it): 2^-42 <= |dt| <= 2^42 (fp32) / 2^-340 <= |dt| <= 2^341 (fp64); it is not checked, and outside that range c1 is what that
+ * header says.  The adaptive form chooses dt itself and does not hold it to this range: a system whose dt_next falls below it takes
+ * that step, its crackles are then without bound or infinite (dt_next = 0: the system ends STALLED) or NaN (bodies the criterion leaves
+ * out), and dt_max is the caller's to keep inside the range.
  *
  * Geometry (nb_hermite6_ensemble_plan_*).  Per system it is nb_hermite6_plan_*'s, a function of (N, precision) alone: a workgroup
  * owns 64 * bodies_per_lane bodies i of ONE system, workgroup g works on tile g mod groups_per_system of system g / groups_per_system,

@@ -122,6 +122,10 @@ def test_block6_argument_errors_are_caught_on_the_host(pkg):
             for eta, eta_start, dt_max, level in ((0, 0.01, 0.125, 30), (-1, 0.01, 0.125, 30), (float("nan"), 0.01, 0.125, 30), (0.2, 0, 0.125, 30), (0.2, float("inf"), 0.125, 30),
                                                   (0.2, 0.01, 0, 30), (0.2, 0.01, float("inf"), 30), (0.2, 0.01, 0.125, -1), (0.2, 0.01, 0.125, 41), (0.2, 0.01, 1e-305, 40)):
                 assert call(params=pkg.HermiteBlockParams(eta, eta_start, dt_max, level, 0)) == ERR, (eta, eta_start, dt_max, level)
+            # the header's "Range of h": a tick or a dt_max whose cube, formed in T, is not a normal T
+            cubes = ((2.0 ** -10, 33), (2.0 ** -3, 40), (1.5 * 2.0 ** -43, 0), (2.0 ** 43, 0)) if dtype == np.float32 else ((2.0 ** -301, 40), (2.0 ** -341, 0), (2.0 ** 342, 0))
+            for dt_max, level in cubes:
+                assert call(params=pkg.HermiteBlockParams(0.2, 0.01, dt_max, level, 0)) == ERR, (dt_max, level)
         assert step(t_stop=float("nan")) == ERR
 
         def sync(**kw):
@@ -132,7 +136,7 @@ def test_block6_argument_errors_are_caught_on_the_host(pkg):
             assert sync(**{null: None}) == ERR, null
         for bad in (dict(n=0), dict(n=MAX_N + 1), dict(pos_out=ok["pos"]), dict(vel_out=ok["vel"] + span - 4 * size), dict(pos_out=0xc00000000), dict(pos_out=0xb00000000 + 2 * size),
                     dict(ticks=ok["ticks"] + 4), dict(status=ok["jerk"]), dict(pos_out=ok["snap"]), dict(vel_out=ok["crackle"] + span - 4 * size), dict(snap=ok["crackle"]),
-                    dict(params=pkg.HermiteBlockParams(0.2, 0.01, 0.125, 41, 0))):
+                    dict(params=pkg.HermiteBlockParams(0.2, 0.01, 0.125, 41, 0)), dict(params=pkg.HermiteBlockParams(0.2, 0.01, *cubes[0], 0))):
             assert sync(**bad) == ERR, bad
         plan = pkg.HermiteBlockPlan()
         for bad in ((0, 1), (MAX_N + 1, 1), (100, 0), (100, 101)):
@@ -268,6 +272,18 @@ def correct6(x, v, a0, j0, s0, a1, j1, s1, h):
     x1 = x + (v + v1) * h / 2 - (a1 - a0) * h ** 2 / 10 + (j0 + j1) * h ** 3 / 120
     c1 = (60 * (a1 - a0 - j0 * h - s0 * h * h / 2) - 36 * (j1 - j0 - s0 * h) * h + 9 * (s1 - s0) * h * h) / h ** 3
     return x1, v1, c1
+
+
+def corrector6_bounds(x, v, a0, j0, s0, a1, j1, s1, v1, h, ba, bj, bs, u):
+    """(bx, bv, bc): the evaluation's bounds ba, bj, bs carried through h/2, h^2/10 and h^3/120 (c1: 60/h^3, 36/h^2, 9/h) plus 2u of the
+    result's term magnitudes (ld_step of tests/test_hermite6.py), all long double, h (n, 1) per body; shared with tests/test_hermite6_domain.py"""
+    A = np.abs
+    h2, t10, t120 = h / 2, h * h / 10, h ** 3 / 120
+    bv = h2 * ba + t10 * bj + t120 * bs + 2 * u * (A(v) + h2 * A(a0 + a1) + t10 * A(j1 - j0) + t120 * A(s0 + s1))
+    bx = h2 * bv + t10 * ba + t120 * bj + 2 * u * (A(x) + h2 * A(v + v1) + t10 * A(a1 - a0) + t120 * A(j0 + j1))
+    mag_c = (60 * (A(a1) + A(a0) + A(j0) * h + A(s0) * h * h / 2) + 36 * (A(j1) + A(j0) + A(s0) * h) * h + 9 * (A(s1) + A(s0)) * h * h) / h ** 3
+    bc = 60 / h ** 3 * ba + 36 / h ** 2 * bj + 9 / h * bs + 2 * u * mag_c
+    return bx, bv, bc
 
 
 def aarseth6(a1, j1, s1, c1, eta, dt_max):
@@ -487,7 +503,13 @@ def test_one_block6_step_stage_by_stage_against_long_double(gpu, dtype, n, n_act
         p = gpu.hermite6_block_plan(n, n_act, dtype)
         assert p.chunks / (p.ranges * p.waves_per_group) > 8, "a wave streams more than kFlushEvery chunks of its range: the flush inside a range is covered"
     pos, vel = cloud(n, dtype, 1000 + n + n_act, mass)
-    eps2, dt_max = dtype(0.01), 0.125
+    check_block6_stages_of(gpu, pos, vel, dtype(0.01), n_act, mass, eta)
+
+
+def check_block6_stages_of(gpu, pos, vel, eps2, n_act, mass, eta, dt_max=0.125):
+    """one block step of n_act due bodies among the T-typed state (pos, vel) (hand_made_schedule), every stage against long double; `mass`
+    names the state in the messages; shared with tests/test_hermite6_domain.py"""
+    dtype, n = pos.dtype.type, pos.shape[0]
     tol, u = LD(TOL[dtype]), LD(UNIT_ROUNDOFF[dtype])
     now, max_level, active, levels, ticks = hand_made_schedule(n, n_act, n * 7 + n_act)
     params = gpu.HermiteBlockParams(eta, 0.01, dt_max, max_level, 0)
@@ -548,12 +570,7 @@ def test_one_block6_step_stage_by_stage_against_long_double(gpu, dtype, n, n_act
     h = ((np.int64(1) << (max_level - levels[sample])) * q).astype(LD)[:, None]
     xs, vs, a0s, j0s, s0s = x[sample], v[sample], a0[sample], j0[sample], s0[sample]
     x1, v1, c1 = correct6(xs, vs, a0s, j0s, s0s, a1, j1, s1, h)
-    # the evaluation's bounds carried through h/2, h^2/10 and h^3/120 (c1: 60/h^3, 36/h^2, 9/h) plus 2u of the result's term magnitudes: ld_step of tests/test_hermite6.py
-    h2, t10, t120 = h / 2, h * h / 10, h ** 3 / 120
-    bv = h2 * ba + t10 * bj + t120 * bs + 2 * u * (A(vs) + h2 * A(a0s + a1) + t10 * A(j1 - j0s) + t120 * A(s0s + s1))
-    bx = h2 * bv + t10 * ba + t120 * bj + 2 * u * (A(xs) + h2 * A(vs + v1) + t10 * A(a1 - a0s) + t120 * A(j0s + j1))
-    mag_c = (60 * (A(a1) + A(a0s) + A(j0s) * h + A(s0s) * h * h / 2) + 36 * (A(j1) + A(j0s) + A(s0s) * h) * h + 9 * (A(s1) + A(s0s)) * h * h) / h ** 3
-    bc = 60 / h ** 3 * ba + 36 / h ** 2 * bj + 9 / h * bs + 2 * u * mag_c
+    bx, bv, bc = corrector6_bounds(xs, vs, a0s, j0s, s0s, a1, j1, s1, v1, h, ba, bj, bs, u)
     for name, g, w, b in zip(("position", "velocity", "acceleration", "jerk", "snap", "crackle"), got, (x1, v1, a1, j1, s1, c1), (bx, bv, ba, bj, bs, bc)):
         err = np.abs(g[sample, :3].astype(LD) - w)
         print(f"n {n} n_act {n_act} {mass}: {name} at {worst_fraction(err, b):.3g} of its bound")

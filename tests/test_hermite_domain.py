@@ -757,25 +757,54 @@ def test_shared_time_step_at_extreme_magnitudes(gpu, dtype, e, low):
         assert abs(LD(dts[s]) - rule) <= 2 * u * rule, (s, dts[s], rule)
 
 
+def timestep6_arrays(dtype, e):
+    """300 hand-made accelerations, jerks, snaps and crackles whose norms are 2^e, 2^-e and 1 in turn; beyond the range (e > 250) body 2
+    has |a|^2 and |c|^2 underflow to 0 beside products that do not -- it gives the step the surviving products give"""
+    rng = np.random.default_rng(103 + e)
+    n = 300
+    arrays = [rng.standard_normal((n, 4)) + 2 for _ in range(4)]
+    scale = np.where(np.arange(n) % 3 == 0, 2.0 ** e, np.where(np.arange(n) % 3 == 1, 2.0 ** -e, 1.0))[:, None]
+    arrays = [(q * scale).astype(dtype) for q in arrays]
+    if e > 250:
+        for q, p2 in zip(arrays, (-600, -100, 400, -600)):
+            q[2] *= 2.0 ** p2
+    for q in arrays:
+        q[:, 3] = 0
+    return arrays
+
+
+def timestep6_rule(arrays, e, eta):
+    """(the step in long double, the rows that count): inside the header's range Aarseth's rule over all bodies; beyond it the header's
+    outcome -- the expression in plain fp64, bodies with a bad denominator or ratio left out, which are the ordinary bodies and body 2"""
+    n = arrays[0].shape[0]
+    a, j, s, c = (norm(q[:, :3].astype(LD)) for q in arrays)
+    ratio = (a * s + j * j) / (j * c + s * s)
+    ordinary = None
+    if e > 250:
+        ordinary = np.flatnonzero(np.arange(n) % 3 == 2)
+        with np.errstate(all="ignore"):
+            a2, j2, s2, c2 = ((q[:, :3].astype(np.float64) ** 2).sum(axis=1) for q in arrays)
+            den = np.sqrt(j2 * c2) + s2
+            plain = (np.sqrt(a2 * s2) + j2) / den
+        kept = (den > 0) & np.isfinite(plain)
+        assert set(np.flatnonzero(kept)) == set(ordinary) and np.argmin(np.where(kept, plain, np.inf)) == 2 and plain[2] < ratio[2] / 1.5
+        ratio = plain[kept].astype(LD)
+    return LD(eta) * np.sqrt(ratio.min()), ordinary
+
+
+TIMESTEP6_CASES = [(np.float32, 100), (np.float64, 100), (np.float64, 245), (np.float64, 600)]
+
+
 @gpu_only
-@pytest.mark.parametrize("dtype,e", [(np.float32, 100), (np.float64, 100), (np.float64, 245), (np.float64, 600)])
+@pytest.mark.parametrize("dtype,e", TIMESTEP6_CASES)
 def test_hermite6_time_step_on_both_sides_of_its_range(gpu, dtype, e):
     """nb_hermite6_timestep_* forms plain fp64 products of two norms.  Inside the header's range (fp32: always; fp64: norms within
     2^+-250) it follows Aarseth's rule to the bound of tests/test_hermite6.py; beyond it (2^+-600) a body whose products overflow, or
     all underflow to 0, is left out -- the result is that of the other bodies alone, bit for bit, never NaN -- and a body of which
     only some products underflow gives the step the surviving ones give (here a smaller one than the exact rule's)."""
     f, scalar = hermite6_fns(gpu, dtype)
-    rng = np.random.default_rng(103 + e)
     n, eta = 300, dtype(0.02)
-    arrays = [rng.standard_normal((n, 4)) + 2 for _ in range(4)]
-    scale = np.where(np.arange(n) % 3 == 0, 2.0 ** e, np.where(np.arange(n) % 3 == 1, 2.0 ** -e, 1.0))[:, None]
-    beyond = e > 250
-    arrays = [(q * scale).astype(dtype) for q in arrays]
-    if beyond:  # body 2: |a|^2 and |c|^2 underflow to 0 beside products that do not -- it gives the step the surviving products give
-        for q, p2 in zip(arrays, (-600, -100, 400, -600)):
-            q[2] *= 2.0 ** p2
-    for q in arrays:
-        q[:, 3] = 0
+    arrays = timestep6_arrays(dtype, e)
 
     def timestep(rows):
         zeros = np.zeros((len(rows), 4), dtype)
@@ -789,21 +818,14 @@ def test_hermite6_time_step_on_both_sides_of_its_range(gpu, dtype, e):
         return dt
 
     got = timestep(np.arange(n))
-    a, j, s, c = (norm(q[:, :3].astype(LD)) for q in arrays)
-    ratio = (a * s + j * j) / (j * c + s * s)
-    if beyond:
-        ordinary = np.flatnonzero(np.arange(n) % 3 == 2)
+    want, ordinary = timestep6_rule(arrays, e, eta)
+    if ordinary is not None:
         assert got.tobytes() == timestep(ordinary).tobytes() and np.isfinite(got) and got > 0
-        with np.errstate(all="ignore"):  # the header's outcome: the expression in plain fp64, bodies with a bad denominator or ratio left out
-            a2, j2, s2, c2 = ((q[:, :3].astype(np.float64) ** 2).sum(axis=1) for q in arrays)
-            den = np.sqrt(j2 * c2) + s2
-            plain = (np.sqrt(a2 * s2) + j2) / den
-        kept = (den > 0) & np.isfinite(plain)
-        assert set(np.flatnonzero(kept)) == set(ordinary) and np.argmin(np.where(kept, plain, np.inf)) == 2 and plain[2] < ratio[2] / 1.5
-        ratio = plain[kept].astype(LD)
-    want = LD(eta) * np.sqrt(ratio.min())
-    allowed = 2 * float(np.finfo(np.float32).eps) if dtype == np.float32 else 1e-14
+    allowed = TIMESTEP6_ALLOWED[dtype]
     assert abs(LD(got) - want) <= allowed * want, (got, want)
+
+
+TIMESTEP6_ALLOWED = {np.float32: 2 * float(np.finfo(np.float32).eps), np.float64: 1e-14}
 
 
 @pytest.mark.parametrize("dtype,e,low", TIMESTEP_CASES)
