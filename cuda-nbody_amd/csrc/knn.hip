@@ -281,14 +281,15 @@ __global__ __launch_bounds__(64 * S) void knn_search(const T* pos, unsigned n, u
         }
         if (!with_density) continue;
         const double dk   = static_cast<double>(slot_of<T, CAP>(ld[k], last));
-        const bool   good = dk > 0.0 && dk < infinity<double>();
+        const double cube = dk * __builtin_sqrt(dk), volume = NB_KNN_SPHERE * cube;
+        const bool   good = cube >= 0x1p-1022 && volume < infinity<double>();  // a positive NORMAL cube, a finite volume (fp64: d_K^2 from ~2^-681.3 to ~2^681.2)
         double       mass = 0.0;  // the K - 1 inner neighbours, in rank order
 #pragma unroll
         for (int s = 0; s + 1 < CAP; ++s) {
             const unsigned j = lj[k][s];
             if (good && static_cast<unsigned>(s) < last && j < n) mass += static_cast<double>(pos[4 * static_cast<size_t>(j) + 3]);
         }
-        const double rho = good ? mass / (NB_KNN_SPHERE * (dk * __builtin_sqrt(dk))) : 0.0;
+        const double rho = good ? mass / volume : 0.0;
         rho_out[i]       = rho;
         if (densities != nullptr) densities[i] = static_cast<T>(rho);
         defined += good ? 1u : 0u, degenerate += good ? 0u : 1u;

@@ -29,8 +29,9 @@
  *
  *                rho_i = M_i / (c * (d_K^2 * sqrt(d_K^2))),    c = 4.188790204786391 (NB_KNN_SPHERE, the double nearest 4 pi / 3)
  *
- * rho_i is DEFINED AS 0 when d_K^2 is 0, +inf or missing (fewer than K neighbours).  Such bodies are counted in the record
- * (`degenerate`), and NB_KNN_DEGENERATE says there were any.  Densities and the record need K >= 2; with K = 1 they are refused.
+ * rho_i is DEFINED AS 0 when d_K^2 is 0, +inf or missing (fewer than K neighbours), or when the cube d_K^2 * sqrt(d_K^2) is not a
+ * positive normal double or c times it is not finite (fp64 only: below).  Such bodies are counted in the record (`degenerate`), and NB_KNN_DEGENERATE says there
+ * were any.  Densities and the record need K >= 2; with K = 1 they are refused.
  *
  * THE STRUCTURE RECORD (doubles and 32-bit counts; every sum in an order fixed by the plan, so the bits repeat from call to call):
  *   sum_density      sum rho_i
@@ -45,6 +46,23 @@
  *                    radii are then NaN.
  * The density radius and the core radius are the two definitions of a "core radius" in use: the density-weighted mean distance
  * and the density-squared-weighted rms distance from the density centre.
+ *
+ * Operand range.  The lists hold for EVERY input, subnormal and overflowed d2 included: the "Operand range" of nbody_hip_neighbour.h,
+ * which is about the same d2.  Ranks past the candidates with a d2 below +inf hold NB_NEIGHBOUR_NONE and +inf.  The masses take no part
+ * in the lists.
+ * The density is given by the formula for d_K^2 in [2^-681, 2^681), where the cube is a normal double and c times it finite whatever
+ * the mantissa (the rule itself is the one above, on the cube and the product as computed).  In fp32 that is every d_K^2 from the
+ * smallest subnormal to the largest finite float.  In fp64 a smaller d_K^2 (its cube is subnormal, or 0 below 2^-716) or a larger one
+ * (c times its cube is +inf, from 2^683 the cube itself) is `degenerate` and has the density 0 -- never +inf, and never a 0 that the
+ * formula's own overflow made and that is counted as `defined`.  A defined rho_i is a normal double unless M_i / (c * cube) leaves
+ * the range: M_i > 16 at the lower edge, M_i < 4 at the upper one; a NaN or infinite mass reaches the densities of the bodies that
+ * have it among their K - 1 inner neighbours, and through them the record's sums.  `densities` in fp32 is the double rounded once:
+ * +inf above FLT_MAX (unit masses: d_K^2 below about 2^-87), subnormal or 0 below FLT_MIN; the double is what the record is made of.
+ * The record squares rho_i.  Its sums are what the formulas say while every nonzero rho_i, rho_i |x_i|, rho_i |x_i - x_d|, rho_i^2 and
+ * rho_i^2 |x_i - x_d|^2, and the sum of each, is a normal double: rho_i within [2^-511, 2^511] less the room the sums need, which for
+ * unit masses and a state of the size of d_K is d_K^2 in [2^-342, 2^339).  In fp32, with masses within 2^+-100, that is always so.
+ * Outside it nothing is clamped: the counts, the extremes, the densest body and the flags stay exact, the sums and the two radii are
+ * what IEEE arithmetic gives (+inf, or NaN from inf / inf and 0 / 0).
  *
  * Geometry (nb_knn_plan_*) and workspace (nb_knn_workspace_bytes): functions of (N, K, precision) alone.  A workgroup of the search
  * owns one tile of 64 * bodies_per_lane bodies i; its S waves split the chunks of 128 bodies j (chunk c -> wave c mod S), each keeps

@@ -23,7 +23,8 @@
  *   nearest_dist_sq[i]  T         that d2; +inf if there is none
  *   counts[i]           unsigned  the number of j != i with d2(i, j) < r2_i (strict)
  *   potentials[i]       T         -sum_{j != i} m_j / sqrt(d2(i, j) + softening_sq); NULL: no v_rsq is spent.  At softening_sq = 0 a
- *                                 coincident distinct pair gives -inf, as the formula says.  The order of the sum is fixed by the
+ *                                 coincident distinct pair gives -inf, as the formula says; so does a pair whose d2 + softening_sq is
+ *                                 SUBNORMAL (below: Operand range).  The order of the sum is fixed by the
  *                                 geometry (nb_neighbour_plan_*), so the bits repeat from call to call.
  *   r2_i is `radius_sq`, or radii_sq[i] when radii_sq != NULL (a device array T[N]: one-sided "gather" lists).  The caller passes
  *   SQUARED radii, so no rounding of a square is left undefined.  A NaN or negative r2_i in the array counts nobody.
@@ -44,6 +45,21 @@
  *   max_count, max_count_body   the largest count and the LOWEST body that has it (0, 0 when all counts are 0)
  *   flags              NB_NEIGHBOUR_OVERFLOW or 0
  * So a caller finds the hardest encounter of a 262 144-body state by reading 64 bytes.
+ *
+ * Operand range.  The exact outputs -- nearest_index, nearest_dist_sq, counts, the lists, the status record -- hold for EVERY input:
+ * d2 is IEEE arithmetic in T with subnormals kept, in fp32 too, and every comparison sees it as it is.  So a subnormal d2 is not 0 (it is
+ * less than a larger subnormal radius and not less than one equal to it), a d2 that overflows is +inf and nobody's neighbour, even at a
+ * radius of +inf, and a NaN d2 (a NaN coordinate; two bodies at the same infinity) is nobody's neighbour either.  A body at an infinity
+ * has no nearest neighbour and is in no list; -0.0 and +0.0 are one place.  The masses take no part in any of these.
+ * The potentials are held to the formula while s2 = d2 + softening_sq is in [2^-126, 2^128) (fp32) / [2^-1022, 2^1021) (fp64): the
+ * normal range of T, less the three binades at the top of fp64 in which the square of the v_rsq_f64 seed is subnormal.  One term is
+ * then within 1e-6 (fp32) / 1e-14 (fp64) of -m_j / sqrt(s2) rounded to T (measured: 1.5e-7 / 3.0e-16); the measured
+ * error in those three binades of fp64 is no larger.  A SUBNORMAL s2 is outside the range in both precisions:
+ * v_rsq_f32 takes a subnormal operand as 0, and in fp64 the square of the seed is infinite below s2 = 2^-1024.  The term is then
+ * -m_j * inf: -inf, as for a coincident pair at softening_sq = 0, and NaN where m_j is 0 (fp64 is still finite and within the bound
+ * for a subnormal s2 above 2^-1024).  A pair with s2 = +inf adds m_j * 0, and so does the body's own slot, j = i: 0 for a finite mass.  So
+ * a NaN or infinite mass makes every potential non-finite, its body's own included (-inf or NaN from the other bodies', NaN where s2 is
+ * +inf and at its own), and reaches nothing else.
  *
  * Geometry (nb_neighbour_plan_*): a function of (N, precision) alone, never of the device, the stream or the outputs asked for.  The
  * survey's workgroups own one tile of 64 * bodies_per_lane bodies i (an aligned chunk of bodies j, or half of one in fp64); their S

@@ -8,7 +8,8 @@ The definitions, restated in numpy below.  With d2(i, j) = dx dx + (dy dy + dz d
 
 and in double (numpy_density, numpy_structure), with d_K^2 the K-th d2 and M_i the masses of the K - 1 inner neighbours added in rank order:
 
-    rho_i = M_i / (c (d_K^2 sqrt(d_K^2))),  c = 4.188790204786391;   rho_i = 0 when d_K^2 is 0, +inf or missing (`degenerate`)
+    rho_i = M_i / (c (d_K^2 sqrt(d_K^2))),  c = 4.188790204786391;   rho_i = 0 when d_K^2 is 0, +inf or missing, or when the cube is not a
+    positive normal double or c times it is not finite (`degenerate`)
     sum_density = sum rho,  centre = sum rho x / sum rho,  density_radius = sum rho |x - centre| / sum rho,
     core_radius = sqrt(sum rho^2 |x - centre|^2 / sum rho^2),  the largest rho and its lowest body,  the smallest and largest finite d_K^2
 
@@ -66,14 +67,32 @@ def numpy_density(pos, index, dist, k):
     """-> rho (N,) float64, defined (N,) bool, from the first k columns of the lists"""
     n = pos.shape[0]
     dk = dist[:, k - 1].astype(np.float64)
-    good = (dk > 0) & (dk < np.inf)
+    with np.errstate(over="ignore", under="ignore"):
+        cube = dk * np.sqrt(dk)
+        volume = SPHERE * cube
+    good = (cube >= np.finfo(np.float64).tiny) & (volume < np.inf)  # a positive normal cube, a finite volume: never for d_K^2 of 0, +inf or missing
     mass = np.zeros(n)
-    for rank in range(k - 1):  # (rank order)
-        j = np.minimum(index[:, rank], n - 1)
-        mass = mass + np.where(good, pos[j, 3].astype(np.float64), 0.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rho = np.where(good, mass / (SPHERE * (dk * np.sqrt(dk))), 0.0)
+    with np.errstate(invalid="ignore"):
+        for rank in range(k - 1):  # (rank order)
+            j = np.minimum(index[:, rank], n - 1)
+            mass = mass + np.where(good, pos[j, 3].astype(np.float64), 0.0)
+    with np.errstate(all="ignore"):
+        rho = np.where(good, mass / volume, 0.0)
     return rho, good
+
+
+def rho_ld(pos, index, dist, k):
+    """-> rho (N,) long double, defined (N,) bool: numpy_density with x87 range and precision through the mass sum, the cube and the
+    quotient.  Which bodies are `defined` is the header's rule, stated on the DOUBLE cube; where it holds the long double cube is normal too."""
+    n = pos.shape[0]
+    good = numpy_density(pos, index, dist, k)[1]
+    dk = np.where(good, dist[:, k - 1], 1).astype(np.longdouble)
+    mass = np.zeros(n, np.longdouble)
+    with np.errstate(invalid="ignore"):
+        for rank in range(k - 1):
+            j = np.minimum(index[:, rank], n - 1)
+            mass = mass + np.where(good, pos[j, 3].astype(np.longdouble), 0)
+        return np.where(good, mass / (np.longdouble(SPHERE) * (dk * np.sqrt(dk))), 0), good
 
 
 def numpy_structure(pos, rho, good, dk, kind=np.float64):
