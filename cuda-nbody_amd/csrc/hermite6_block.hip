@@ -16,7 +16,8 @@
 // read on the device; wave 0 stores the partial sums, in units of the reference mass, to planes [J][9][slots] -- around hermite6_eval's
 // streaming loops: hermite_stream.inc with nine sums and hermite6_interaction.inc, a body j three adjacent vec4 by scalar loads, 47 / 48
 // v_pk_* + 2 v_rsq_f32 per packed pair, no LDS, barrier or scratch inside the loops.  Compiled, as hermite6_eval, for 4 (fp32) / 3 (fp64)
-// waves per SIMD.  hermite6_block_finish adds the planes (range_sum.inc) and applies hermite6_eval's corrector with the body's own step.
+// waves per SIMD.  hermite6_block_finish adds the planes (range_sum.inc) and applies hermite6_eval's corrector with the body's own step
+// (hermite6_correct.inc).  Around that arithmetic the kernels are hermite_block.hip's text: hermite_block_parts.inc.
 #include "hermite6_block_kernels.h"
 #include "hermite6_kernels.h"
 
@@ -45,42 +46,16 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
     using LT             = Lane<T>;
     using vec4           = typename LT::vec4;
     using vec            = typename LT::vec;
-    using raw4           = typename LT::raw4;
     using bits           = typename LT::bits;
     constexpr int W      = LT::W;  // bodies i per lane
     constexpr int U      = hermite6_unroll_for<T>();
     constexpr int STRIDE = 3;  // vec4 per body of state12
-    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx4/x8/x16
-
-    if (ctrl->go == 0) return;
-    const unsigned  n_act = ctrl->n_act;
-    const BlockGeom geom  = stream_geometry(n, n_act, 64 * W, kBlockTarget);
-    if (blockIdx.x >= geom.tiles * geom.ranges) return;
-    const unsigned ranges = geom.ranges;
-    const unsigned tile   = blockIdx.x / ranges;
-    const unsigned range  = blockIdx.x % ranges;
-    const unsigned slots  = geom.tiles * (64 * W);
-
-    const T* const   pos_base = state12;
-    const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state12));
-    const int        tid  = threadIdx.x;
-    const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int        lane = tid & 63;
-
-    // bodies i of this lane: slots tile_base + k*64 + lane of the active list
-    const unsigned tile_base = tile * (64 * W);
-    vec            px, py, pz, vx, vy, vz, ax, ay, az;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        const unsigned slot = tile_base + k * 64 + lane;
-        const size_t   i    = active[slot < n_act ? slot : n_act - 1];
-        const vec4     p    = reinterpret_cast<const vec4*>(state12)[3 * i];
-        const vec4     v    = reinterpret_cast<const vec4*>(state12)[3 * i + 1];
-        const vec4     b    = reinterpret_cast<const vec4*>(state12)[3 * i + 2];
-        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
-        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
-        LT::set(ax, k, b.x), LT::set(ay, k, b.y), LT::set(az, k, b.z);
-    }
+    const unsigned local = blockIdx.x;
+    const T* const state = state12;
+#define BLOCK_PART_EVAL_HEAD
+#include "hermite_block_parts.inc"
+#define BLOCK_PART_EVAL_BODIES
+#include "hermite_block_parts.inc"
     vec eps2 = LT::splat(eps2_in);
     LT::keep_in_vgpr(eps2);
 
@@ -89,36 +64,22 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
 #define HERMITE_STREAM_INTERACTION "hermite6_interaction.inc"
 #define HERMITE_STREAM_UNIT_SUMS  // the partial planes are in units of the reference mass; the finish kernel multiplies
 #include "hermite_stream.inc"
-
-    // planes [J][9][slots]: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) partial[(static_cast<size_t>(range) * 9 + q) * slots + tile_base + k * 64 + lane] = LT::get(second[q], k);
-    }
+#define BLOCK_PART_EVAL_STORE
+#include "hermite_block_parts.inc"
 }
 
 // ---- the predictor ------------------------------------------------------------------------------------------------------------------------
 
-// One body to dt, Horner to the crackle: the expressions of hermite6_predict (hermite6_eval.hip).  dt = 0 gives the stored bits.
+// One body to dt: hermite6_predict's expressions (hermite6_predict.inc).  dt = 0 gives the stored bits.
 template <typename T> struct Predicted6 {
     typename Lane<T>::vec4 x, v, a;  // {x_p, m}, {v_p, 0}, {a_p, 0}
 };
 template <typename T>
 __device__ __forceinline__ Predicted6<T> predict6_body(const typename Lane<T>::vec4& x, const typename Lane<T>::vec4& v, const typename Lane<T>::vec4& a,
                                                        const typename Lane<T>::vec4& j, const typename Lane<T>::vec4& s, const typename Lane<T>::vec4& c, T dt) {
-    const T       h2 = dt * T(0.5), h3 = dt * (T(1) / T(3)), h4 = dt * T(0.25), h5 = dt * T(0.2);
-    Predicted6<T> o;
-    auto          component = [&](T xq, T vq, T aq, T jq, T sq, T cq, T& xpq, T& vpq, T& apq) {
-        xpq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, __builtin_fma(h4, __builtin_fma(h5, cq, sq), jq), aq), vq), xq);
-        vpq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, __builtin_fma(h4, cq, sq), jq), aq), vq);
-        apq = __builtin_fma(dt, __builtin_fma(h2, __builtin_fma(h3, cq, sq), jq), aq);
-    };
-    component(x.x, v.x, a.x, j.x, s.x, c.x, o.x.x, o.v.x, o.a.x);
-    component(x.y, v.y, a.y, j.y, s.y, c.y, o.x.y, o.v.y, o.a.y);
-    component(x.z, v.z, a.z, j.z, s.z, c.z, o.x.z, o.v.z, o.a.z);
-    o.x.w = x.w, o.v.w = 0, o.a.w = 0;
-    return o;
+    using vec4 = typename Lane<T>::vec4;
+#include "hermite6_predict.inc"
+    return {xp, vp, ap};
 }
 
 template <typename T> __global__ __launch_bounds__(256) void block6_predict_count(Block6Args<T> a, unsigned partials) {
@@ -133,19 +94,12 @@ template <typename T> __global__ __launch_bounds__(256) void block6_predict_coun
         if (next < m.next) m.next = next;
         if (k > m.level) m.level = k;
     }
-    m                            = block_fold(m, lds_next, lds_level);
-    const unsigned long long now = m.next;
-    const double             q   = tick_length(a.p);
-    const bool               go  = static_cast<double>(now) * q <= a.t_stop;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        a.ctrl->now = now, a.ctrl->go = go ? 1u : 0u;
-        if (!go) a.ctrl->n_act = 0;
-        const unsigned flags    = a.status->flags;
-        a.status->flags         = go ? (flags & ~kBlockStopped) : (flags | kBlockStopped);
-        const int deepest       = a.status->deepest_level;
-        a.status->deepest_level = m.level > deepest ? m.level : deepest;
-    }
-    if (!go) return;
+    m = block_fold(m, lds_next, lds_level);
+    const unsigned block = blockIdx.x;
+#define BLOCK_CTRL a.ctrl
+#define BLOCK_STATUS a.status
+#define BLOCK_PART_DECIDE
+#include "hermite_block_parts.inc"
     const unsigned i      = blockIdx.x * 256u + threadIdx.x;
     bool           active = false;
     if (i < a.n) {
@@ -158,10 +112,7 @@ template <typename T> __global__ __launch_bounds__(256) void block6_predict_coun
         vec4* const              out  = reinterpret_cast<vec4*>(a.state12) + 3 * static_cast<size_t>(i);
         out[0] = o.x, out[1] = o.v, out[2] = o.a;
     }
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
-    __syncthreads();
-    if (threadIdx.x == 0) a.counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    block_count(active, wave_count, a.counts, blockIdx.x);
 }
 
 // ---- the finish -----------------------------------------------------------------------------------------------------------------------
@@ -176,53 +127,23 @@ template <typename V> __device__ __forceinline__ double aarseth6_dt(const V& a1,
 
 template <typename T> __global__ __launch_bounds__(256) void hermite6_block_finish(Block6Args<T> a) {
     using vec4 = typename Lane<T>::vec4;
-    constexpr unsigned per_tile = 64 * Lane<T>::W;
-    if (a.ctrl->go == 0) return;
-    const unsigned n_act = a.ctrl->n_act;
-    const unsigned slot  = blockIdx.x * 256u + threadIdx.x;
-    if (slot >= n_act) return;
-    const BlockGeom          geom  = stream_geometry(a.n, n_act, per_tile, kBlockTarget);
-    const size_t             slots = static_cast<size_t>(geom.tiles) * per_tile;
-    const unsigned long long now   = a.ctrl->now;
-    const size_t             i     = a.active[slot];
-    // sum[9]: the J ranges' partial sums of this slot, in range order
-    constexpr int            NS      = 9;
-    const T* const           partial = a.partial;
-    const unsigned           ranges  = geom.ranges;
-#include "range_sum.inc"
-    const T m_first = a.state12[3];
-    const T m_ref   = usable_unit(m_first) ? m_first : T(1);
-    vec4    a1, j1, s1;
-    a1.x = sum[0] * m_ref, a1.y = sum[1] * m_ref, a1.z = sum[2] * m_ref, a1.w = 0;
-    j1.x = sum[3] * m_ref, j1.y = sum[4] * m_ref, j1.z = sum[5] * m_ref, j1.w = 0;
-    s1.x = sum[6] * m_ref, s1.y = sum[7] * m_ref, s1.z = sum[8] * m_ref, s1.w = 0;
-
-    int                      k     = a.levels[i];
-    k                              = k < 0 ? 0 : (k > a.p.max_level ? a.p.max_level : k);
-    const double             q     = tick_length(a.p);
-    const unsigned long long own   = 1ull << (a.p.max_level - k);
-    const double             dt_i  = static_cast<double>(own) * q;
-    // the corrector and the crackle of nb_hermite6_step_* (hermite6_eval's epilogue), with the body's own step
-    const T    h = static_cast<T>(dt_i), h2 = h * T(0.5), hh = h * h, t10 = hh * T(0.1), h3 = hh * h, t120 = h3 * (T(1) / T(120));
-    const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
-    vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
-    const vec4 a0 = reinterpret_cast<const vec4*>(a.acc)[i];
-    const vec4 j0 = reinterpret_cast<const vec4*>(a.jerk)[i];
-    const vec4 s0 = reinterpret_cast<const vec4*>(a.snap)[i];
-    vec4       x1, c1;
-    auto       component = [&](T xq, T& vq, T a0q, T j0q, T s0q, T a1q, T j1q, T s1q, T& x1q, T& c1q) {
-        const T v1 = vq + __builtin_fma(h2, a0q + a1q, __builtin_fma(t120, s0q + s1q, -t10 * (j1q - j0q)));
-        x1q        = xq + __builtin_fma(h2, vq + v1, __builtin_fma(t120, j0q + j1q, -t10 * (a1q - a0q)));
-        const T d0 = __builtin_fma(-h2 * h, s0q, __builtin_fma(-h, j0q, a1q - a0q));
-        const T d1 = __builtin_fma(-h, s0q, j1q - j0q) * h;
-        const T d2 = (s1q - s0q) * hh;
-        c1q        = __builtin_fma(T(9), d2, __builtin_fma(T(-36), d1, T(60) * d0)) / h3;
-        vq         = v1;
-    };
-    component(x.x, v.x, a0.x, j0.x, s0.x, a1.x, j1.x, s1.x, x1.x, c1.x);
-    component(x.y, v.y, a0.y, j0.y, s0.y, a1.y, j1.y, s1.y, x1.y, c1.y);
-    component(x.z, v.z, a0.z, j0.z, s0.z, a1.z, j1.z, s1.z, x1.z, c1.z);
-    x1.w = x.w, c1.w = 0;
+    const BlockCtrl* const ctrl  = a.ctrl;
+    const unsigned         block = blockIdx.x;
+#define BLOCK_PART_FINISH_HEAD
+#include "hermite_block_parts.inc"
+    constexpr int  NS      = 9;
+    const size_t   i       = a.active[slot];
+    const T* const state   = a.state12;
+    const T* const partial = a.partial;
+#define BLOCK_PART_FINISH_SUMS
+#include "hermite_block_parts.inc"
+    // the corrector and the crackle of nb_hermite6_step_* (hermite6_eval's epilogue), with the body's own step, in place
+    const struct {
+        const T *old_pos, *vel, *acc, *jerk, *snap;
+    } stored{a.pos, a.vel, a.acc, a.jerk, a.snap};
+#define HERMITE6_STEP_DT static_cast<T>(dt_i)
+#define HERMITE6_STORED(array) stored.array
+#include "hermite6_correct.inc"
     reinterpret_cast<vec4*>(a.pos)[i]     = x1;
     reinterpret_cast<vec4*>(a.vel)[i]     = v;
     reinterpret_cast<vec4*>(a.acc)[i]     = a1;
@@ -231,13 +152,8 @@ template <typename T> __global__ __launch_bounds__(256) void hermite6_block_fini
     reinterpret_cast<vec4*>(a.crackle)[i] = c1;
 
     const double dt_a = aarseth6_dt(a1, j1, s1, c1, a.p.eta, a.p.dt_max);
-    if (dt_a < dt_i) {
-        while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > dt_a) ++k;
-    } else if (dt_a >= 2.0 * dt_i && k > 0 && now % (2 * own) == 0) {
-        --k;
-    }
-    a.levels[i] = k;
-    a.ticks[i]  = now;
+#define BLOCK_PART_FINISH_LEVEL
+#include "hermite_block_parts.inc"
 }
 
 // init: levels from the accelerations and jerks nb_hermite6_init's launches left, ticks 0, the status record cleared
@@ -252,12 +168,7 @@ template <typename T> __global__ __launch_bounds__(256) void block6_init_levels(
     }
     if (i >= a.n) return;
     const vec4   acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
-    const double want0 = a.p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
-    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : a.p.dt_max;
-    const double q     = tick_length(a.p);
-    int          k     = 0;
-    while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > want) ++k;
-    a.levels[i] = k;
+    a.levels[i] = first_level(acc, jerk, a.p);
     a.ticks[i]  = 0;
 }
 

@@ -5,23 +5,16 @@
 #include "capi_check.h"
 #include "hermite6_block_kernels.h"
 #include "hermite6_kernels.h"
+#include "hermite_block_boundary.h"
 #include "softening_floor.h"
-
-#include <cmath>
 
 namespace {
 
 using nb::floored, nb::Span, nb::spans_ok;
 
-static_assert(NB_HERMITE_BLOCK_MAX_BODIES == nb::kBlockMaxBodies, "the header's limit is the kernels'");
-static_assert(NB_HERMITE_BLOCK_MAX_LEVEL == nb::kBlockMaxLevel, "the header's deepest level is the kernels'");
-static_assert(NB_HERMITE_BLOCK_STOPPED == nb::kBlockStopped, "the header's flag is the kernels'");
-static_assert(sizeof(nb_hermite_block_status_t) == 64 && sizeof(nb::BlockStatus) == 64, "the status record is 64 bytes");
-static_assert(sizeof(nb_hermite_block_params_t) == sizeof(nb::BlockParams), "the parameters cross by value");
-static_assert(sizeof(nb::BlockCtrl) == 64, "the control record is 64 bytes");
 static_assert(nb::kBlockMaxBodies <= nb::kHermite6MaxBodies, "the initial evaluation takes every N the block steps take");
 
-bool size_ok(unsigned n) { return n >= 1 && n <= nb::kBlockMaxBodies; }
+nb::BlockLayout layout(unsigned n, size_t size_t_of) { return nb::block_layout(n, size_t_of, 3, nb::kBlock6Sums); }  // a predicted body is three vec4
 
 // the cube of a step, as the corrector forms it in T (hh = h * h, h3 = hh * h): c1 divides by it
 template <typename T> bool cube_is_normal(double step) {
@@ -31,34 +24,14 @@ template <typename T> bool cube_is_normal(double step) {
 
 // T: the corrector's precision.  The longest step (dt_max) and the shortest (one tick) must have normal cubes in T.
 template <typename T> bool params_ok(const nb_hermite_block_params_t* p) {
-    if (p == nullptr) return false;
-    const auto positive = [](double v) { return std::isfinite(v) && v > 0; };
-    if (!(positive(p->eta) && positive(p->eta_start) && positive(p->dt_max) && p->max_level >= 0 && p->max_level <= nb::kBlockMaxLevel)) return false;
-    const double tick = std::ldexp(p->dt_max, -p->max_level);
-    return std::isnormal(tick) && cube_is_normal<T>(tick) && cube_is_normal<T>(p->dt_max);
+    return nb::block_params_ok(p) && cube_is_normal<T>(std::ldexp(p->dt_max, -p->max_level)) && cube_is_normal<T>(p->dt_max);
 }
 
-nb::BlockParams params_of(const nb_hermite_block_params_t* p) { return nb::BlockParams{p->eta, p->eta_start, p->dt_max, p->max_level, 0}; }
-
 template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_block_plan_t* out) {
-    if (out == nullptr || !size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
-    constexpr unsigned  per_tile = sizeof(T) == 4 ? 128 : 64;
-    const nb::BlockGeom g        = nb::block_geometry(n, n_active, per_tile);
-    const unsigned      S        = nb::block_waves(n);
-    out->bodies_per_lane         = per_tile / 64;
-    out->waves_per_group         = static_cast<int>(S);
-    out->unroll                  = nb::hermite6_unroll_for<T>();
-    out->tiles                   = g.tiles;
-    out->ranges                  = g.ranges;
-    out->groups                  = g.tiles * g.ranges;
-    out->launch_groups           = nb::block_launch_groups(n, per_tile);
-    out->block_threads           = 64 * S;
-    out->lds_bytes               = static_cast<unsigned>((S > 1 ? S - 1 : 1) * nb::kBlock6Sums * per_tile * sizeof(T)) + 128;
-    out->slots                   = g.tiles * per_tile;
-    out->chunks                  = nb::block_chunks(n);
-    out->launches                = 6;
-    out->partial_offset          = nb::block6_layout(n, sizeof(T)).partial;
-    out->partial_bytes           = static_cast<unsigned long long>(g.ranges) * nb::kBlock6Sums * out->slots * sizeof(T);
+    if (out == nullptr || !nb::block_size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
+    nb::block_plan_fill(out, n, n_active, sizeof(T), nb::kBlock6Sums, nb::hermite6_unroll_for<T>());
+    out->launches       = 6;
+    out->partial_offset = layout(n, sizeof(T)).partial;
     return 0;
 }
 
@@ -66,8 +39,8 @@ template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_b
 template <typename T>
 bool bind(nb::Block6Args<T>& a, T* pos, T* vel, T* acc, T* jerk, T* snap, T* crackle, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace,
           size_t workspace_bytes, unsigned n, const nb_hermite_block_params_t* params) {
-    if (!size_ok(n) || !params_ok<T>(params)) return false;
-    const nb::Block6Layout l = nb::block6_layout(n, sizeof(T));
+    if (!nb::block_size_ok(n) || !params_ok<T>(params)) return false;
+    const nb::BlockLayout l = layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return false;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al}, {crackle, bodies, al},
@@ -79,7 +52,7 @@ bool bind(nb::Block6Args<T>& a, T* pos, T* vel, T* acc, T* jerk, T* snap, T* cra
     a.ticks    = reinterpret_cast<unsigned long long*>(ticks);
     a.levels   = levels;
     a.status   = reinterpret_cast<nb::BlockStatus*>(status);
-    a.state12  = reinterpret_cast<T*>(ws + l.state12);
+    a.state12  = reinterpret_cast<T*>(ws + l.state);
     a.partial  = reinterpret_cast<T*>(ws + l.partial);
     a.active   = reinterpret_cast<unsigned*>(ws + l.active);
     a.counts   = reinterpret_cast<unsigned*>(ws + l.counts);
@@ -87,7 +60,7 @@ bool bind(nb::Block6Args<T>& a, T* pos, T* vel, T* acc, T* jerk, T* snap, T* cra
     a.lvl_part = reinterpret_cast<int*>(ws + l.lvl_part);
     a.ctrl     = reinterpret_cast<nb::BlockCtrl*>(ws + l.ctrl);
     a.n        = n;
-    a.p        = params_of(params);
+    a.p        = nb::block_params_of(params);
     a.t_stop   = 0;
     return true;
 }
@@ -123,14 +96,14 @@ int step(T* pos, T* vel, T* acc, T* jerk, T* snap, T* crackle, uint64_t* ticks, 
 template <typename T>
 int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const T* snap, const T* crackle, const uint64_t* ticks,
          const nb_hermite_block_status_t* status, unsigned n, const nb_hermite_block_params_t* params, nb_stream_t stream) {
-    if (!size_ok(n) || !params_ok<T>(params)) return NB_ERR_INVALID_ARGUMENT;
+    if (!nb::block_size_ok(n) || !params_ok<T>(params)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos_out, bodies, al}, {vel_out, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al},
                    {crackle, bodies, al}, {ticks, static_cast<std::uintptr_t>(n) * 8, 8}, {status, 64, 8}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     return static_cast<int>(nb::launch_block6_sync<T>(pos_out, vel_out, pos, vel, acc, jerk, snap, crackle, reinterpret_cast<const unsigned long long*>(ticks),
-                                                      reinterpret_cast<const nb::BlockStatus*>(status), n, params_of(params), static_cast<hipStream_t>(stream)));
+                                                      reinterpret_cast<const nb::BlockStatus*>(status), n, nb::block_params_of(params), static_cast<hipStream_t>(stream)));
 }
 
 }  // namespace
@@ -138,8 +111,8 @@ int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const
 extern "C" {
 
 int nb_hermite6_block_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
-    *bytes = nb::block6_layout(num_bodies, sizeof_T).bytes;
+    if (bytes == nullptr || !nb::block_size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
+    *bytes = layout(num_bodies, sizeof_T).bytes;
     return 0;
 }
 

@@ -8,27 +8,7 @@
 
 namespace nb {
 
-inline constexpr unsigned kBlock6Sums = 9;  // ax ay az jx jy jz sx sy sz
-
-// ---- workspace layout (byte offsets, each section on a 256-byte boundary): block_layout with 12 T per body and 9 planes --------------
-struct Block6Layout {
-    size_t state12, partial, active, counts, min_part, lvl_part, ctrl, bytes;
-};
-inline Block6Layout block6_layout(unsigned n, size_t size_t_of) {
-    const unsigned per_tile = size_t_of == 4 ? 128 : 64;
-    const auto     up       = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-    Block6Layout   l;
-    size_t         at = 0;
-    l.state12 = at, at += up(static_cast<size_t>(n) * 12 * size_t_of);
-    l.partial = at, at += up(static_cast<size_t>(block_launch_groups(n, per_tile)) * kBlock6Sums * per_tile * size_t_of);
-    l.active = at, at += up(static_cast<size_t>(n) * 4);
-    l.counts = at, at += up(static_cast<size_t>((n + kBlockThreads - 1) / kBlockThreads) * 4);
-    l.min_part = at, at += up(kBlockMinPartials * 8);
-    l.lvl_part = at, at += up(kBlockMinPartials * 4);
-    l.ctrl = at, at += up(sizeof(BlockCtrl));
-    l.bytes = at;
-    return l;
-}
+inline constexpr unsigned kBlock6Sums = 9;  // ax ay az jx jy jz sx sy sz: block_layout's planes, with three vec4 per predicted body
 
 template <typename T> struct Block6Args {
     T *                 pos, *vel, *acc, *jerk, *snap, *crackle;  // stored state T[4N]

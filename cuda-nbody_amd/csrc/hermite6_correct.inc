@@ -1,9 +1,9 @@
-// hermite6_correct.inc -- the STEP epilogue of one body: the 6th-order corrector, the new crackle and their stores, as text.  One text for
-// hermite6_eval (hermite6_eval.hip) and hermite6_ensemble_eval (hermite6_ensemble.hip).  The includer has defined T, vec4, the body's index i,
-// the evaluation's a1, j1, s1 (vec4 each) and two macros, which this file undefines:
+// hermite6_correct.inc -- the 6th-order corrector and the new crackle of one body, as text.  One text for hermite6_eval (hermite6_eval.hip),
+// hermite6_ensemble_eval (hermite6_ensemble.hip) and hermite6_block_finish (hermite6_block.hip).  The includer has defined T, vec4, the
+// body's index i, the evaluation's a1, j1, s1 (vec4 each) and two macros, which this file undefines:
 //   HERMITE6_STEP_DT          the step
-//   HERMITE6_STORED(array)    the array of the stored state -- old_pos, new_pos, vel, acc, jerk, snap, crackle -- that index i counts in
-// x1 -> new_pos; v1 and c1 in place.  (a1, j1 and s1 are stored by the includer, STEP or not.)
+//   HERMITE6_STORED(array)    the array of the stored state -- old_pos, vel, acc, jerk, snap -- that index i counts in
+// It gets: x1, v replaced by v1, and c1.  The includer stores them, in an order of its own (the listings of the three differ in it).
             // v1 = v + (a0 + a1) h/2 - (j1 - j0) h^2/10 + (s0 + s1) h^3/120,   x1 = x + (v + v1) h/2 - (a1 - a0) h^2/10 + (j0 + j1) h^3/120
             // c1, the third derivative at the step's end of the quintic through (a, j, s) at both ends:
             //   D0 = a1 - a0 - j0 h - s0 h^2/2,  D1 = (j1 - j0 - s0 h) h,  D2 = (s1 - s0) h^2,  c1 = (60 D0 - 36 D1 + 9 D2) / h^3
@@ -28,8 +28,5 @@
             component(x.y, v.y, a0.y, j0.y, s0.y, a1.y, j1.y, s1.y, x1.y, c1.y);
             component(x.z, v.z, a0.z, j0.z, s0.z, a1.z, j1.z, s1.z, x1.z, c1.z);
             x1.w = x.w, c1.w = 0;
-            reinterpret_cast<vec4*>(HERMITE6_STORED(new_pos))[i] = x1;
-            reinterpret_cast<vec4*>(HERMITE6_STORED(vel))[i]     = v;
-            reinterpret_cast<vec4*>(HERMITE6_STORED(crackle))[i] = c1;
 #undef HERMITE6_STEP_DT
 #undef HERMITE6_STORED

@@ -109,6 +109,9 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
 #define HERMITE6_STEP_DT dt_late
 #define HERMITE6_STORED(array) (e.array + origin)
 #include "hermite6_correct.inc"
+            reinterpret_cast<vec4*>(e.new_pos + origin)[i] = x1;
+            reinterpret_cast<vec4*>(e.vel + origin)[i]     = v;
+            reinterpret_cast<vec4*>(e.crackle + origin)[i] = c1;
         }
         reinterpret_cast<vec4*>(e.acc + origin)[i]  = a1;
         reinterpret_cast<vec4*>(e.jerk + origin)[i] = j1;

@@ -92,6 +92,9 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
 #define HERMITE6_STEP_DT e.dt
 #define HERMITE6_STORED(array) e.array
 #include "hermite6_correct.inc"
+            reinterpret_cast<vec4*>(e.new_pos)[i] = x1;
+            reinterpret_cast<vec4*>(e.vel)[i]     = v;
+            reinterpret_cast<vec4*>(e.crackle)[i] = c1;
         }
         reinterpret_cast<vec4*>(e.acc)[i]  = a1;
         reinterpret_cast<vec4*>(e.jerk)[i] = j1;

@@ -20,7 +20,8 @@
 // [J][6][tiles 64 W].  (tile, range) come from n_act, which the workgroup reads from the control record: the launch grid is sized for the
 // worst n_act of this N and the workgroups beyond tiles J leave.  The kernel below is the active list, the tile / range derivation
 // (stream_geometry, wave_stream.h), the include, and the plane store.  hermite_block_finish adds the planes (range_sum.inc) and corrects
-// (hermite_correct.inc); the predictor of block_predict_count and block_sync is hermite_body.h's.
+// (hermite_correct.inc); the predictor of block_predict_count and block_sync is hermite_body.h's.  What these kernels share with
+// hermite6_block.hip and hermite_block_ensemble.hip around that arithmetic is hermite_block_parts.inc and hermite_block_kernels_shared.h.
 #include "hermite_block_kernels.h"
 
 namespace nb {
@@ -40,53 +41,24 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     using LT         = Lane<T>;
     using vec4       = typename LT::vec4;
     using vec        = typename LT::vec;
-    using raw4       = typename LT::raw4;
     using bits       = typename LT::bits;
     constexpr int W      = LT::W;  // bodies i per lane
     constexpr int U      = unroll_for<T>();
     constexpr int STRIDE = 2;  // vec4 per body of state8
-    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx8 / x16
-
-    if (ctrl->go == 0) return;
-    const unsigned  n_act = ctrl->n_act;
-    const BlockGeom geom  = stream_geometry(n, n_act, 64 * W, kBlockTarget);
-    if (blockIdx.x >= geom.tiles * geom.ranges) return;
-    const unsigned ranges = geom.ranges;
-    const unsigned tile   = blockIdx.x / ranges;
-    const unsigned range  = blockIdx.x % ranges;
-    const unsigned slots  = geom.tiles * (64 * W);
-
-    const T* const   pos_base = state8;
-    const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state8));
-    const int        tid  = threadIdx.x;
-    const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int        lane = tid & 63;
-
-    // bodies i of this lane: slots tile_base + k*64 + lane of the active list
-    const unsigned tile_base = tile * (64 * W);
-    vec            px, py, pz, vx, vy, vz;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        const unsigned slot = tile_base + k * 64 + lane;
-        const size_t   i    = active[slot < n_act ? slot : n_act - 1];
-        const vec4     p    = reinterpret_cast<const vec4*>(state8)[2 * i];
-        const vec4     v    = reinterpret_cast<const vec4*>(state8)[2 * i + 1];
-        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
-        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
-    }
+    const unsigned local = blockIdx.x;
+    const T* const state = state8;
+#define BLOCK_PART_EVAL_HEAD
+#include "hermite_block_parts.inc"
+#define BLOCK_PART_EVAL_BODIES
+#include "hermite_block_parts.inc"
     vec eps2 = LT::splat(eps2_in);
     LT::keep_in_vgpr(eps2);
 
     auto body_j = [&](size_t j, BodyJ<T>& b) { b.p = jp[2 * j], b.v = jp[2 * j + 1]; };  // adjacent: one s_load_dwordx8 / x16
 #define HERMITE_STREAM_UNIT_SUMS  // the partial planes are in units of the reference mass; the finish kernel multiplies
 #include "hermite_stream.inc"
-
-    // planes [J][6][slots]: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) partial[(static_cast<size_t>(range) * 6 + q) * slots + tile_base + k * 64 + lane] = LT::get(second[q], k);
-    }
+#define BLOCK_PART_EVAL_STORE
+#include "hermite_block_parts.inc"
 }
 
 // ---- the schedule ---------------------------------------------------------------------------------------------------------------------
@@ -105,19 +77,12 @@ template <typename T> __global__ __launch_bounds__(256) void block_predict_count
         if (next < m.next) m.next = next;
         if (k > m.level) m.level = k;
     }
-    m                            = block_fold(m, lds_next, lds_level);
-    const unsigned long long now = m.next;
-    const double             q   = tick_length(a.p);
-    const bool               go  = static_cast<double>(now) * q <= a.t_stop;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        a.ctrl->now = now, a.ctrl->go = go ? 1u : 0u;
-        if (!go) a.ctrl->n_act = 0;
-        const unsigned flags    = a.status->flags;
-        a.status->flags         = go ? (flags & ~kBlockStopped) : (flags | kBlockStopped);
-        const int deepest       = a.status->deepest_level;
-        a.status->deepest_level = m.level > deepest ? m.level : deepest;
-    }
-    if (!go) return;
+    m = block_fold(m, lds_next, lds_level);
+    const unsigned block = blockIdx.x;
+#define BLOCK_CTRL a.ctrl
+#define BLOCK_STATUS a.status
+#define BLOCK_PART_DECIDE
+#include "hermite_block_parts.inc"
     const unsigned i      = blockIdx.x * 256u + threadIdx.x;
     bool           active = false;
     if (i < a.n) {
@@ -131,40 +96,22 @@ template <typename T> __global__ __launch_bounds__(256) void block_predict_count
         reinterpret_cast<vec4*>(a.state8)[2 * static_cast<size_t>(i)]     = xp;
         reinterpret_cast<vec4*>(a.state8)[2 * static_cast<size_t>(i) + 1] = vp;
     }
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
-    __syncthreads();
-    if (threadIdx.x == 0) a.counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    block_count(active, wave_count, a.counts, blockIdx.x);
 }
 
 template <typename T> __global__ __launch_bounds__(256) void hermite_block_finish(BlockArgs<T> a) {
     using vec4 = typename Lane<T>::vec4;
-    constexpr unsigned per_tile = 64 * Lane<T>::W;
-    if (a.ctrl->go == 0) return;
-    const unsigned n_act = a.ctrl->n_act;
-    const unsigned slot  = blockIdx.x * 256u + threadIdx.x;
-    if (slot >= n_act) return;
-    const BlockGeom          geom  = stream_geometry(a.n, n_act, per_tile, kBlockTarget);
-    const size_t             slots = static_cast<size_t>(geom.tiles) * per_tile;
-    const unsigned long long now   = a.ctrl->now;
-    const size_t             i     = a.active[slot];
-    // sum[6]: the J ranges' partial sums of this slot, in range order
-    constexpr int            NS      = 6;
-    const T* const           partial = a.partial;
-    const unsigned           ranges  = geom.ranges;
-#include "range_sum.inc"
-    const T m_first = a.state8[3];
-    const T m_ref   = usable_unit(m_first) ? m_first : T(1);
-    vec4    a1, j1;
-    a1.x = sum[0] * m_ref, a1.y = sum[1] * m_ref, a1.z = sum[2] * m_ref, a1.w = 0;
-    j1.x = sum[3] * m_ref, j1.y = sum[4] * m_ref, j1.z = sum[5] * m_ref, j1.w = 0;
-
-    int                      k     = a.levels[i];
-    k                              = k < 0 ? 0 : (k > a.p.max_level ? a.p.max_level : k);
-    const double             q     = tick_length(a.p);
-    const unsigned long long own   = 1ull << (a.p.max_level - k);
-    const double             dt_i  = static_cast<double>(own) * q;
-    const T                  dt    = static_cast<T>(dt_i);
+    const BlockCtrl* const ctrl  = a.ctrl;
+    const unsigned         block = blockIdx.x;
+#define BLOCK_PART_FINISH_HEAD
+#include "hermite_block_parts.inc"
+    constexpr int  NS      = 6;
+    const size_t   i       = a.active[slot];
+    const T* const state   = a.state8;
+    const T* const partial = a.partial;
+#define BLOCK_PART_FINISH_SUMS
+#include "hermite_block_parts.inc"
+    const T    dt = static_cast<T>(dt_i);
     // the corrector of nb_hermite_step_*, with the body's own dt
     const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
     vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
@@ -177,13 +124,8 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_block_finis
     reinterpret_cast<vec4*>(a.jerk)[i] = j1;
 
     const double dt_a = aarseth_dt(a0, j0, a1, j1, dt_i, a.p.eta, a.p.dt_max);
-    if (dt_a < dt_i) {
-        while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > dt_a) ++k;
-    } else if (dt_a >= 2.0 * dt_i && k > 0 && now % (2 * own) == 0) {
-        --k;
-    }
-    a.levels[i] = k;
-    a.ticks[i]  = now;
+#define BLOCK_PART_FINISH_LEVEL
+#include "hermite_block_parts.inc"
 }
 
 // init: levels from the accelerations and jerks nb_hermite_eval left, ticks 0, the status record cleared
@@ -198,12 +140,7 @@ template <typename T> __global__ __launch_bounds__(256) void block_init_levels(B
     }
     if (i >= a.n) return;
     const vec4   acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
-    const double want0 = a.p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
-    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : a.p.dt_max;
-    const double q     = tick_length(a.p);
-    int          k     = 0;
-    while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > want) ++k;
-    a.levels[i] = k;
+    a.levels[i] = first_level(acc, jerk, a.p);
     a.ticks[i]  = 0;
 }
 

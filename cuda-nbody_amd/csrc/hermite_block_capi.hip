@@ -1,55 +1,22 @@
 // hermite_block_capi.hip -- the extern "C" boundary of libnbody_hip_hermite_block.so (include/nbody_hip_hermite_block.h).  Every
 // argument is checked on the host before the first HIP call; a call then launches, allocates nothing, takes no lock and never
 // synchronises.  The initial evaluation is hermite_eval.o's (linked in; that object exports nothing).
-#include "../../include/nbody_hip_hermite_block.h"
 #include "capi_check.h"
-#include "hermite_block_kernels.h"
+#include "hermite_block_boundary.h"
 #include "hermite_kernels.h"
 #include "softening_floor.h"
-
-#include <cmath>
 
 namespace {
 
 using nb::floored, nb::Span, nb::spans_ok;
 
-static_assert(NB_HERMITE_BLOCK_MAX_BODIES == nb::kBlockMaxBodies, "the header's limit is the kernels'");
-static_assert(NB_HERMITE_BLOCK_MAX_LEVEL == nb::kBlockMaxLevel, "the header's deepest level is the kernels'");
-static_assert(NB_HERMITE_BLOCK_STOPPED == nb::kBlockStopped, "the header's flag is the kernels'");
-static_assert(sizeof(nb_hermite_block_status_t) == 64 && sizeof(nb::BlockStatus) == 64, "the status record is 64 bytes");
-static_assert(sizeof(nb_hermite_block_params_t) == sizeof(nb::BlockParams), "the parameters cross by value");
-static_assert(sizeof(nb::BlockCtrl) == 64, "the control record is 64 bytes");
-
-bool size_ok(unsigned n) { return n >= 1 && n <= nb::kBlockMaxBodies; }
-
-bool params_ok(const nb_hermite_block_params_t* p) {
-    if (p == nullptr) return false;
-    const auto positive = [](double v) { return std::isfinite(v) && v > 0; };
-    return positive(p->eta) && positive(p->eta_start) && positive(p->dt_max) && p->max_level >= 0 && p->max_level <= nb::kBlockMaxLevel &&
-           std::isnormal(std::ldexp(p->dt_max, -p->max_level));
-}
-
-nb::BlockParams params_of(const nb_hermite_block_params_t* p) { return nb::BlockParams{p->eta, p->eta_start, p->dt_max, p->max_level, 0}; }
+nb::BlockLayout layout(unsigned n, size_t size_t_of) { return nb::block_layout(n, size_t_of, 2, nb::kBlockSums); }  // a predicted body is two vec4
 
 template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_block_plan_t* out) {
-    if (out == nullptr || !size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
-    constexpr unsigned  per_tile = sizeof(T) == 4 ? 128 : 64;
-    const nb::BlockGeom g        = nb::block_geometry(n, n_active, per_tile);
-    const unsigned      S        = nb::block_waves(n);
-    out->bodies_per_lane         = per_tile / 64;
-    out->waves_per_group         = static_cast<int>(S);
-    out->unroll                  = sizeof(T) == 4 ? 4 : 2;
-    out->tiles                   = g.tiles;
-    out->ranges                  = g.ranges;
-    out->groups                  = g.tiles * g.ranges;
-    out->launch_groups           = nb::block_launch_groups(n, per_tile);
-    out->block_threads           = 64 * S;
-    out->lds_bytes               = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * per_tile * sizeof(T)) + 128;
-    out->slots                   = g.tiles * per_tile;
-    out->chunks                  = nb::block_chunks(n);
-    out->launches                = 6;
-    out->partial_offset          = nb::block_layout(n, sizeof(T)).partial;
-    out->partial_bytes           = static_cast<unsigned long long>(g.ranges) * 6 * out->slots * sizeof(T);
+    if (out == nullptr || !nb::block_size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
+    nb::block_plan_fill(out, n, n_active, sizeof(T), nb::kBlockSums, sizeof(T) == 4 ? 4 : 2);
+    out->launches       = 6;
+    out->partial_offset = layout(n, sizeof(T)).partial;
     return 0;
 }
 
@@ -57,8 +24,8 @@ template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_b
 template <typename T>
 bool bind(nb::BlockArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace, size_t workspace_bytes,
           unsigned n, const nb_hermite_block_params_t* params) {
-    if (!size_ok(n) || !params_ok(params)) return false;
-    const nb::BlockLayout l = nb::block_layout(n, sizeof(T));
+    if (!nb::block_size_ok(n) || !nb::block_params_ok(params)) return false;
+    const nb::BlockLayout l = layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return false;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {ticks, static_cast<std::uintptr_t>(n) * 8, 8},
@@ -70,7 +37,7 @@ bool bind(nb::BlockArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks,
     a.ticks    = reinterpret_cast<unsigned long long*>(ticks);
     a.levels   = levels;
     a.status   = reinterpret_cast<nb::BlockStatus*>(status);
-    a.state8   = reinterpret_cast<T*>(ws + l.state8);
+    a.state8   = reinterpret_cast<T*>(ws + l.state);
     a.partial  = reinterpret_cast<T*>(ws + l.partial);
     a.active   = reinterpret_cast<unsigned*>(ws + l.active);
     a.counts   = reinterpret_cast<unsigned*>(ws + l.counts);
@@ -78,7 +45,7 @@ bool bind(nb::BlockArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks,
     a.lvl_part = reinterpret_cast<int*>(ws + l.lvl_part);
     a.ctrl     = reinterpret_cast<nb::BlockCtrl*>(ws + l.ctrl);
     a.n        = n;
-    a.p        = params_of(params);
+    a.p        = nb::block_params_of(params);
     a.t_stop   = 0;
     return true;
 }
@@ -109,14 +76,14 @@ int step(T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_h
 template <typename T>
 int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const uint64_t* ticks, const nb_hermite_block_status_t* status, unsigned n,
          const nb_hermite_block_params_t* params, nb_stream_t stream) {
-    if (!size_ok(n) || !params_ok(params)) return NB_ERR_INVALID_ARGUMENT;
+    if (!nb::block_size_ok(n) || !nb::block_params_ok(params)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos_out, bodies, al}, {vel_out, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al},
                    {ticks, static_cast<std::uintptr_t>(n) * 8, 8}, {status, 64, 8}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     return static_cast<int>(nb::launch_block_sync<T>(pos_out, vel_out, pos, vel, acc, jerk, reinterpret_cast<const unsigned long long*>(ticks),
-                                                     reinterpret_cast<const nb::BlockStatus*>(status), n, params_of(params), static_cast<hipStream_t>(stream)));
+                                                     reinterpret_cast<const nb::BlockStatus*>(status), n, nb::block_params_of(params), static_cast<hipStream_t>(stream)));
 }
 
 }  // namespace
@@ -124,8 +91,8 @@ int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const
 extern "C" {
 
 int nb_hermite_block_workspace_bytes(unsigned num_bodies, unsigned sizeof_T, size_t* bytes) {
-    if (bytes == nullptr || !size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
-    *bytes = nb::block_layout(num_bodies, sizeof_T).bytes;
+    if (bytes == nullptr || !nb::block_size_ok(num_bodies) || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
+    *bytes = layout(num_bodies, sizeof_T).bytes;
     return 0;
 }
 

@@ -57,64 +57,33 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     using LT         = Lane<T>;
     using vec4       = typename LT::vec4;
     using vec        = typename LT::vec;
-    using raw4       = typename LT::raw4;
     using bits       = typename LT::bits;
     constexpr int W      = LT::W;  // bodies i per lane
     constexpr int U      = unroll_for<T>();
     constexpr int STRIDE = 2;  // vec4 per body of state8
-    typedef const raw4 __attribute__((address_space(4)))* stream_ptr;  // read-only for the whole launch -> s_load_dwordx8 / x16
 
     // the workgroup's system, and its index among that system's workgroups (wave-uniform: the whole workgroup leaves together)
     const unsigned system = blockIdx.x / a.groups_per_system;
     const unsigned local  = blockIdx.x - system * a.groups_per_system;
     char* const    slice  = a.workspace + static_cast<size_t>(system) * a.stride;
     const BlockCtrl* const ctrl = reinterpret_cast<const BlockCtrl*>(slice + a.ctrl);
-    if (ctrl->go == 0) return;
-    const unsigned  n     = a.n;
-    const unsigned  n_act = ctrl->n_act;
-    const BlockGeom geom  = stream_geometry(n, n_act, 64 * W, kBlockTarget);
-    if (local >= geom.tiles * geom.ranges) return;
-    const unsigned ranges = geom.ranges;
-    const unsigned tile   = local / ranges;
-    const unsigned range  = local % ranges;
-    const unsigned slots  = geom.tiles * (64 * W);
-
-    const T* const        state8  = reinterpret_cast<const T*>(slice + a.state8);
+    const unsigned         n    = a.n;
+#define BLOCK_PART_EVAL_HEAD
+#include "hermite_block_parts.inc"
+    const T* const        state   = reinterpret_cast<const T*>(slice + a.state8);
     const unsigned* const active  = reinterpret_cast<const unsigned*>(slice + a.active);
     T* const              partial = reinterpret_cast<T*>(slice + a.partial);
     const T               eps2_system = floored(a.system_eps2 != nullptr ? uniform_load(a.system_eps2, system) : a.eps2);
-
-    const T* const   pos_base = state8;
-    const stream_ptr jp   = reinterpret_cast<stream_ptr>(reinterpret_cast<unsigned long long>(state8));
-    const int        tid  = threadIdx.x;
-    const int        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int        lane = tid & 63;
-
-    // bodies i of this lane: slots tile_base + k*64 + lane of the system's active list
-    const unsigned tile_base = tile * (64 * W);
-    vec            px, py, pz, vx, vy, vz;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        const unsigned slot = tile_base + k * 64 + lane;
-        const size_t   i    = active[slot < n_act ? slot : n_act - 1];
-        const vec4     p    = reinterpret_cast<const vec4*>(state8)[2 * i];
-        const vec4     v    = reinterpret_cast<const vec4*>(state8)[2 * i + 1];
-        LT::set(px, k, p.x), LT::set(py, k, p.y), LT::set(pz, k, p.z);
-        LT::set(vx, k, v.x), LT::set(vy, k, v.y), LT::set(vz, k, v.z);
-    }
+#define BLOCK_PART_EVAL_BODIES
+#include "hermite_block_parts.inc"
     vec eps2 = LT::splat(eps2_system);
     LT::keep_in_vgpr(eps2);
 
     auto body_j = [&](size_t j, BodyJ<T>& b) { b.p = jp[2 * j], b.v = jp[2 * j + 1]; };  // adjacent: one s_load_dwordx8 / x16
 #define HERMITE_STREAM_UNIT_SUMS  // the partial planes are in units of the reference mass; the finish kernel multiplies
 #include "hermite_stream.inc"
-
-    // planes [J][6][slots] of this system: word (range, q, slot), coalesced across the wave; the slots past n_act of the last tile hold a copy of the last body's sums
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) partial[(static_cast<size_t>(range) * 6 + q) * slots + tile_base + k * 64 + lane] = LT::get(second[q], k);
-    }
+#define BLOCK_PART_EVAL_STORE
+#include "hermite_block_parts.inc"
 }
 
 // ---- the schedule, per system -----------------------------------------------------------------------------------------------------------
@@ -161,21 +130,11 @@ template <typename T> __global__ __launch_bounds__(256) void block_ensemble_pred
         m.next  = reinterpret_cast<const unsigned long long*>(slice + a.layout.min_part)[threadIdx.x];
         m.level = reinterpret_cast<const int*>(slice + a.layout.lvl_part)[threadIdx.x];
     }
-    m                            = block_fold(m, lds_next, lds_level);
-    const unsigned long long now = m.next;
-    const double             q   = tick_length(a.p);
-    const bool               go  = static_cast<double>(now) * q <= a.t_stop;
-    if (block == 0 && threadIdx.x == 0) {
-        BlockCtrl* const   c = ctrl_of(a, system);
-        BlockStatus* const s = a.status + system;
-        c->now = now, c->go = go ? 1u : 0u;
-        if (!go) c->n_act = 0;
-        const unsigned flags = s->flags;
-        s->flags             = go ? (flags & ~kBlockStopped) : (flags | kBlockStopped);
-        const int deepest    = s->deepest_level;
-        s->deepest_level     = m.level > deepest ? m.level : deepest;
-    }
-    if (!go) return;
+    m = block_fold(m, lds_next, lds_level);
+#define BLOCK_CTRL ctrl_of(a, system)
+#define BLOCK_STATUS (a.status + system)
+#define BLOCK_PART_DECIDE
+#include "hermite_block_parts.inc"
     const unsigned local  = block * 256u + threadIdx.x;
     bool           active = false;
     if (local < a.n) {
@@ -191,10 +150,7 @@ template <typename T> __global__ __launch_bounds__(256) void block_ensemble_pred
         state8[2 * static_cast<size_t>(local)]     = xp;
         state8[2 * static_cast<size_t>(local) + 1] = vp;
     }
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
-    __syncthreads();
-    if (threadIdx.x == 0) reinterpret_cast<unsigned*>(slice + a.layout.counts)[block] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    block_count(active, wave_count, reinterpret_cast<unsigned*>(slice + a.layout.counts), block);
 }
 
 // The scan and the scatter in one launch: a system has at most 256 counts, so every workgroup adds those before its own itself (integer
@@ -238,37 +194,19 @@ template <typename T> __global__ __launch_bounds__(256) void block_ensemble_scat
 
 template <typename T> __global__ __launch_bounds__(256) void hermite_block_ensemble_finish(BlockEnsembleArgs<T> a) {
     using vec4 = typename Lane<T>::vec4;
-    constexpr unsigned per_tile = 64 * Lane<T>::W;
-    const unsigned     system = blockIdx.x / a.blocks;
-    const unsigned     block  = blockIdx.x - system * a.blocks;
-    const BlockCtrl*   c      = ctrl_of(a, system);
-    if (c->go == 0) return;
-    const unsigned n_act = c->n_act;
-    const unsigned slot  = block * 256u + threadIdx.x;
-    if (slot >= n_act) return;
-    const BlockGeom          geom   = stream_geometry(a.n, n_act, per_tile, kBlockTarget);
-    const size_t             slots  = static_cast<size_t>(geom.tiles) * per_tile;
-    const unsigned long long now    = c->now;
-    const char* const        slice  = slice_of(a, system);
-    const T* const           state8 = reinterpret_cast<const T*>(slice + a.layout.state8);
-    const size_t             i      = static_cast<size_t>(system) * a.n + reinterpret_cast<const unsigned*>(slice + a.layout.active)[slot];
-    // sum[6]: the J ranges' partial sums of this slot, in range order
-    constexpr int            NS      = 6;
-    const T* const           partial = reinterpret_cast<const T*>(slice + a.layout.partial);
-    const unsigned           ranges  = geom.ranges;
-#include "range_sum.inc"
-    const T m_first = state8[3];
-    const T m_ref   = usable_unit(m_first) ? m_first : T(1);
-    vec4    a1, j1;
-    a1.x = sum[0] * m_ref, a1.y = sum[1] * m_ref, a1.z = sum[2] * m_ref, a1.w = 0;
-    j1.x = sum[3] * m_ref, j1.y = sum[4] * m_ref, j1.z = sum[5] * m_ref, j1.w = 0;
-
-    int                      k     = a.levels[i];
-    k                              = k < 0 ? 0 : (k > a.p.max_level ? a.p.max_level : k);
-    const double             q     = tick_length(a.p);
-    const unsigned long long own   = 1ull << (a.p.max_level - k);
-    const double             dt_i  = static_cast<double>(own) * q;
-    const T                  dt    = static_cast<T>(dt_i);
+    const unsigned         system = blockIdx.x / a.blocks;
+    const unsigned         block  = blockIdx.x - system * a.blocks;
+    const BlockCtrl* const ctrl   = ctrl_of(a, system);
+#define BLOCK_PART_FINISH_HEAD
+#include "hermite_block_parts.inc"
+    constexpr int     NS      = 6;
+    const char* const slice   = slice_of(a, system);
+    const T* const    state   = reinterpret_cast<const T*>(slice + a.layout.state8);
+    const size_t      i       = static_cast<size_t>(system) * a.n + reinterpret_cast<const unsigned*>(slice + a.layout.active)[slot];
+    const T* const    partial = reinterpret_cast<const T*>(slice + a.layout.partial);
+#define BLOCK_PART_FINISH_SUMS
+#include "hermite_block_parts.inc"
+    const T    dt = static_cast<T>(dt_i);
     // the corrector of nb_hermite_step_*, with the body's own dt
     const vec4 x  = reinterpret_cast<const vec4*>(a.pos)[i];
     vec4       v  = reinterpret_cast<const vec4*>(a.vel)[i];
@@ -281,13 +219,8 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_block_ensem
     reinterpret_cast<vec4*>(a.jerk)[i] = j1;
 
     const double dt_a = aarseth_dt(a0, j0, a1, j1, dt_i, a.p.eta, a.p.dt_max);
-    if (dt_a < dt_i) {
-        while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > dt_a) ++k;
-    } else if (dt_a >= 2.0 * dt_i && k > 0 && now % (2 * own) == 0) {
-        --k;
-    }
-    a.levels[i] = k;
-    a.ticks[i]  = now;
+#define BLOCK_PART_FINISH_LEVEL
+#include "hermite_block_parts.inc"
 }
 
 // init: per system, levels from the accelerations and jerks the ensemble evaluation left, ticks 0, the status and control records cleared
@@ -304,12 +237,7 @@ template <typename T> __global__ __launch_bounds__(256) void block_ensemble_init
     if (local >= a.n) return;
     const size_t i     = static_cast<size_t>(system) * a.n + local;
     const vec4   acc = reinterpret_cast<const vec4*>(a.acc)[i], jerk = reinterpret_cast<const vec4*>(a.jerk)[i];
-    const double want0 = a.p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
-    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : a.p.dt_max;
-    const double q     = tick_length(a.p);
-    int          k     = 0;
-    while (k < a.p.max_level && static_cast<double>(1ull << (a.p.max_level - k)) * q > want) ++k;
-    a.levels[i] = k;
+    a.levels[i] = first_level(acc, jerk, a.p);
     a.ticks[i]  = 0;
 }
 

@@ -4,10 +4,9 @@
 // exports nothing).
 #include "../../include/nbody_hip_hermite_block_ensemble.h"
 #include "capi_check.h"
+#include "hermite_block_boundary.h"
 #include "hermite_block_ensemble_kernels.h"
 #include "hermite_ensemble_kernels.h"
-
-#include <cmath>
 
 namespace {
 
@@ -18,11 +17,7 @@ static_assert(NB_HERMITE_BLOCK_ENSEMBLE_MAX_BODIES == nb::kBlockEnsembleMaxBodie
 static_assert(NB_HERMITE_BLOCK_ENSEMBLE_MAX_BODIES == nb::kEnsembleHermiteMaxBodies && NB_HERMITE_BLOCK_ENSEMBLE_MAX_TOTAL == nb::kEnsembleHermiteMaxTotal,
               "... and those of the ensemble evaluation init runs");
 static_assert(nb::kBlockEnsembleMaxBodies <= 256 * nb::kBlockThreads, "a system's counts and partial minima: one per lane of a workgroup of 256");
-static_assert(NB_HERMITE_BLOCK_STOPPED == nb::kBlockStopped, "the header's flag is the kernels'");
-static_assert(sizeof(nb_hermite_block_status_t) == 64 && sizeof(nb::BlockStatus) == 64, "the status record is 64 bytes");
 static_assert(sizeof(nb_hermite_block_ensemble_summary_t) == 64 && sizeof(nb::BlockEnsembleSummary) == 64, "the summary record is 64 bytes");
-static_assert(sizeof(nb_hermite_block_params_t) == sizeof(nb::BlockParams), "the parameters cross by value");
-static_assert(sizeof(nb::BlockCtrl) == 64, "the control record is 64 bytes");
 
 // N, B and their products: every stage of every call is one launch
 template <typename T> bool size_ok(unsigned n, unsigned b) {
@@ -35,40 +30,17 @@ template <typename T> bool size_ok(unsigned n, unsigned b) {
     return eval <= limit && schedule <= limit && first.grid_blocks * first.block_threads <= limit;
 }
 
-bool params_ok(const nb_hermite_block_params_t* p) {
-    if (p == nullptr) return false;
-    const auto positive = [](double v) { return std::isfinite(v) && v > 0; };
-    return positive(p->eta) && positive(p->eta_start) && positive(p->dt_max) && p->max_level >= 0 && p->max_level <= nb::kBlockMaxLevel &&
-           std::isnormal(std::ldexp(p->dt_max, -p->max_level));
-}
-
-nb::BlockParams params_of(const nb_hermite_block_params_t* p) { return nb::BlockParams{p->eta, p->eta_start, p->dt_max, p->max_level, 0}; }
-
 template <typename T> int plan_query(unsigned n, unsigned b, unsigned n_active, nb_hermite_block_ensemble_plan_t* out) {
     if (out == nullptr || !size_ok<T>(n, b) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
-    constexpr unsigned            per_tile = sizeof(T) == 4 ? 128 : 64;
-    const nb::BlockGeom           g        = nb::block_geometry(n, n_active, per_tile);
-    const unsigned                S        = nb::block_waves(n);
-    const nb::BlockEnsembleLayout l        = nb::block_ensemble_layout(n, sizeof(T));
-    out->bodies_per_lane                   = per_tile / 64;
-    out->waves_per_group                   = static_cast<int>(S);
-    out->unroll                            = sizeof(T) == 4 ? 4 : 2;
-    out->tiles                             = g.tiles;
-    out->ranges                            = g.ranges;
-    out->groups                            = g.tiles * g.ranges;
-    out->launch_groups                     = nb::block_launch_groups(n, per_tile);
-    out->block_threads                     = 64 * S;
-    out->lds_bytes                         = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * per_tile * sizeof(T)) + 128;
-    out->slots                             = g.tiles * per_tile;
-    out->chunks                            = nb::block_chunks(n);
-    out->step_launches                     = 5;
-    out->partial_offset                    = l.partial;
-    out->partial_bytes                     = static_cast<unsigned long long>(g.ranges) * 6 * out->slots * sizeof(T);
-    out->groups_per_system                 = out->launch_groups;
-    out->blocks_per_system                 = nb::block_ensemble_blocks(n);
-    out->eval_grid                         = static_cast<unsigned long long>(b) * out->groups_per_system;
-    out->schedule_grid                     = static_cast<unsigned long long>(b) * out->blocks_per_system;
-    out->workspace_stride                  = l.stride;
+    const nb::BlockEnsembleLayout l = nb::block_ensemble_layout(n, sizeof(T));
+    nb::block_plan_fill(out, n, n_active, sizeof(T), nb::kBlockSums, sizeof(T) == 4 ? 4 : 2);
+    out->step_launches     = 5;
+    out->partial_offset    = l.partial;
+    out->groups_per_system = out->launch_groups;
+    out->blocks_per_system = nb::block_ensemble_blocks(n);
+    out->eval_grid         = static_cast<unsigned long long>(b) * out->groups_per_system;
+    out->schedule_grid     = static_cast<unsigned long long>(b) * out->blocks_per_system;
+    out->workspace_stride  = l.stride;
     return 0;
 }
 
@@ -76,7 +48,7 @@ template <typename T> int plan_query(unsigned n, unsigned b, unsigned n_active, 
 template <typename T>
 bool bind(nb::BlockEnsembleArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace, size_t workspace_bytes,
           unsigned n, unsigned b, T eps2, const T* system_eps2, const nb_hermite_block_params_t* params) {
-    if (!size_ok<T>(n, b) || !params_ok(params)) return false;
+    if (!size_ok<T>(n, b) || !nb::block_params_ok(params)) return false;
     const nb::BlockEnsembleLayout l     = nb::block_ensemble_layout(n, sizeof(T));
     const std::uintptr_t          total = static_cast<std::uintptr_t>(l.stride) * b;
     if (workspace_bytes < total) return false;
@@ -97,7 +69,7 @@ bool bind(nb::BlockEnsembleArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t
     a.b                 = b;
     a.blocks            = nb::block_ensemble_blocks(n);
     a.groups_per_system = nb::block_launch_groups(n, sizeof(T) == 4 ? 128 : 64);
-    a.p                 = params_of(params);
+    a.p                 = nb::block_params_of(params);
     a.t_stop            = 0;
     return true;
 }
@@ -126,14 +98,14 @@ int step(T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_h
 template <typename T>
 int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const uint64_t* ticks, const nb_hermite_block_status_t* status, unsigned n, unsigned b,
          const nb_hermite_block_params_t* params, nb_stream_t stream) {
-    if (!size_ok<T>(n, b) || !params_ok(params)) return NB_ERR_INVALID_ARGUMENT;
+    if (!size_ok<T>(n, b) || !nb::block_params_ok(params)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t count = static_cast<std::uintptr_t>(n) * b, bodies = count * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos_out, bodies, al}, {vel_out, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {ticks, count * 8, 8},
                    {status, static_cast<std::uintptr_t>(b) * 64, 8}})) {
         return NB_ERR_INVALID_ARGUMENT;
     }
     return static_cast<int>(nb::launch_block_ensemble_sync<T>(pos_out, vel_out, pos, vel, acc, jerk, reinterpret_cast<const unsigned long long*>(ticks),
-                                                              reinterpret_cast<const nb::BlockStatus*>(status), n, b, params_of(params), static_cast<hipStream_t>(stream)));
+                                                              reinterpret_cast<const nb::BlockStatus*>(status), n, b, nb::block_params_of(params), static_cast<hipStream_t>(stream)));
 }
 
 }  // namespace

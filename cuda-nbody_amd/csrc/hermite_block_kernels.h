@@ -55,16 +55,19 @@ __host__ __device__ inline unsigned block_launch_groups(unsigned n, unsigned per
 }
 
 // ---- workspace layout (byte offsets, each section on a 256-byte boundary) ------------------------------------------------------------
+// One function for both orders: the predicted state has body_vec4 vec4 per body (2; 3 with the acceleration) and there are `sums`
+// partial planes (6; 9 with the snap).
+inline constexpr unsigned kBlockSums = 6;  // ax ay az jx jy jz
 struct BlockLayout {
-    size_t state8, partial, active, counts, min_part, lvl_part, ctrl, bytes;
+    size_t state, partial, active, counts, min_part, lvl_part, ctrl, bytes;
 };
-inline BlockLayout block_layout(unsigned n, size_t size_t_of) {
+inline BlockLayout block_layout(unsigned n, size_t size_t_of, unsigned body_vec4, unsigned sums) {
     const unsigned per_tile = size_t_of == 4 ? 128 : 64;
     const auto     up       = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
     BlockLayout    l;
     size_t         at = 0;
-    l.state8 = at, at += up(static_cast<size_t>(n) * 8 * size_t_of);
-    l.partial = at, at += up(static_cast<size_t>(block_launch_groups(n, per_tile)) * 6 * per_tile * size_t_of);
+    l.state = at, at += up(static_cast<size_t>(n) * 4 * body_vec4 * size_t_of);
+    l.partial = at, at += up(static_cast<size_t>(block_launch_groups(n, per_tile)) * sums * per_tile * size_t_of);
     l.active = at, at += up(static_cast<size_t>(n) * 4);
     l.counts = at, at += up(static_cast<size_t>((n + kBlockThreads - 1) / kBlockThreads) * 4);
     l.min_part = at, at += up(kBlockMinPartials * 8);

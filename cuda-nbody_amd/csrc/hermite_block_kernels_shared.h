@@ -1,7 +1,8 @@
 // hermite_block_kernels_shared.h -- the small device helpers of the block time step scheme, one text for hermite_block.hip
-// (nb_hermite_block_*) and hermite_block_ensemble.hip (nb_hermite_block_ensemble_*): the ticks of a level, the length of a tick, the
-// minimum / deepest-level fold of a workgroup of 256, and Aarseth's step.  Included inside each translation unit's own anonymous namespace,
-// after hermite_block_kernels.h (BlockParams).
+// (nb_hermite_block_*), hermite6_block.hip (nb_hermite6_block_*) and hermite_block_ensemble.hip (nb_hermite_block_ensemble_*): the ticks of
+// a level, the length of a tick, the minimum / deepest-level fold and the active count of a workgroup of 256, the level a run starts at,
+// and Aarseth's step.  Included inside each translation unit's own anonymous namespace, after hermite_block_kernels.h (BlockParams).
+// (What the listings did not allow as functions is text: hermite_block_parts.inc.)
 #pragma once
 
 __device__ __forceinline__ unsigned long long ticks_of(int level, int max_level) {
@@ -33,7 +34,27 @@ __device__ __forceinline__ MinLevel block_fold(MinLevel m, unsigned long long* l
     return MinLevel{lds_next[0], lds_level[0]};
 }
 
+// the number of active lanes of a workgroup of 256 -> counts[block]
+__device__ __forceinline__ void block_count(bool active, unsigned* wave_count, unsigned* counts, unsigned block) {
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(active);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = static_cast<unsigned>(__builtin_popcountll(mask));
+    __syncthreads();
+    if (threadIdx.x == 0) counts[block] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+}
+
 __device__ __forceinline__ double norm3(double x, double y, double z) { return __builtin_sqrt(x * x + y * y + z * z); }
+
+// level k deepened until its step is no longer than `want` (q: the length of a tick)
+__device__ __forceinline__ int deepened(int k, double want, const BlockParams& p, double q) {
+    while (k < p.max_level && static_cast<double>(1ull << (p.max_level - k)) * q > want) ++k;
+    return k;
+}
+// the level a run starts at: the longest step within eta_start |a| / |jerk|, dt_max where that is no positive number
+template <typename V> __device__ __forceinline__ int first_level(const V& acc, const V& jerk, const BlockParams& p) {
+    const double want0 = p.eta_start * norm3(acc.x, acc.y, acc.z) / norm3(jerk.x, jerk.y, jerk.z);
+    const double want  = (want0 == want0 && want0 - want0 == 0 && want0 > 0) ? want0 : p.dt_max;
+    return deepened(0, want, p, tick_length(p));
+}
 
 // Aarseth's step from the stored T-typed a0, j0, a1, j1, in fp64 (include/nbody_hip_hermite_block.h)
 template <typename V> __device__ __forceinline__ double aarseth_dt(const V& a0, const V& j0, const V& a1, const V& j1, double h, double eta, double dt_max) {
