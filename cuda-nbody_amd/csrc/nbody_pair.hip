@@ -43,10 +43,20 @@
 //
 // Results differ from the one-sided FAST kernel in summation order only; both are held to an fp64 direct sum by the tests.
 #include "nbody_kernels.h"
+#include "nbody_pair_lead.h"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
+
+// A variant build of this unit (tools/build_pair_variant.sh recompiles nbody_pair.hip alone under its flags: stamps, non-temporal planes,
+// no balancing, another unroll or stage block) is a build of pair_forces: its one-GPU step launches pair_forces at every size, never the
+// headline geometry's own kernel (nbody_pair_lead.hip), so that the flag changes the kernel that runs and the stamps are its stamps.
+#if defined(NB_PAIR_STAMPS) || defined(NB_PAIR_NONTEMPORAL) || defined(NB_NO_BALANCE) || defined(NB_PAIR_NO_QUARTERS) || defined(NB_PAIR_UNR) || defined(NB_PAIR_RB)
+#define NB_PAIR_VARIANT_BUILD 1
+#else
+#define NB_PAIR_VARIANT_BUILD 0
+#endif
 
 #ifdef NB_PAIR_STAMPS
 // Diagnostic build only (tools/build_pair_variant.sh stamps "-DNB_PAIR_STAMPS", read by tools/pair_stamps.py): per wave of the LAST
@@ -58,46 +68,11 @@ extern "C" __attribute__((visibility("default"))) int nb_debug_read_pair_stamps(
 }
 #endif
 
-// The workspace planes (reaction sums, i-side sums) are written once by pair_forces and read once by pair_finish / pair_reduce.  With
-// -DNB_PAIR_NONTEMPORAL (tools/build_pair_variant.sh; the A/B of round 6: profiles/round6_nontemporal_ab.txt) those accesses carry the
-// non-temporal hint, so that the streaming planes do not evict the 4 MiB position array from each XCD's L2.  Without the flag: plain accesses.
-#ifdef NB_PAIR_NONTEMPORAL
-#define NB_WS_STORE(ptr, value) __builtin_nontemporal_store((value), (ptr))
-#define NB_WS_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define NB_WS_STORE(ptr, value) (*(ptr) = (value))
-#define NB_WS_LOAD(ptr) (*(ptr))
-#endif
-
 namespace nb {
 namespace {
 
 #include "nbody_lane.h"
-
-// ---- rotation of whatever belongs to the body j: one lane onward (lane l reads lane l-1; lane 0 reads lane 63) --------------
-constexpr int kWaveRor1 = 0x13C;
-// (The same rotation on the LDS crossbar -- ds_bpermute_b32, off the vector ALU -- was tried: 10.36 against 10.08 ms, same box.)
-__device__ __forceinline__ int rotate_bits(int v) { return __builtin_amdgcn_update_dpp(v, v, kWaveRor1, 0xf, 0xf, false); }
-__device__ __forceinline__ float rotate(float x) { return __builtin_bit_cast(float, rotate_bits(__builtin_bit_cast(int, x))); }
-__device__ __forceinline__ double rotate(double x) {
-    const unsigned long long b  = __builtin_bit_cast(unsigned long long, x);
-    const unsigned           l2 = static_cast<unsigned>(rotate_bits(static_cast<int>(b & 0xffffffffull)));
-    const unsigned           h2 = static_cast<unsigned>(rotate_bits(static_cast<int>(b >> 32)));
-    return __builtin_bit_cast(double, (static_cast<unsigned long long>(h2) << 32) | l2);
-}
-__device__ __forceinline__ v2f rotate(v2f x) { return v2f{rotate(x.x), rotate(x.y)}; }
-
-// lane 0's value, as a wave-uniform (scalar) value
-__device__ __forceinline__ float first_lane(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
-__device__ __forceinline__ double first_lane(double x) {
-    const unsigned long long b  = __builtin_bit_cast(unsigned long long, x);
-    const unsigned           lo = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(b & 0xffffffffull)));
-    const unsigned           hi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(b >> 32)));
-    return __builtin_bit_cast(double, (static_cast<unsigned long long>(hi) << 32) | lo);
-}
-
-__device__ __forceinline__ float  both_halves(v2f a) { return a.x + a.y; }
-__device__ __forceinline__ double both_halves(double a) { return a; }
+#include "nbody_pair_lane.h"  // rotate, first_lane, both_halves, NB_WS_STORE / NB_WS_LOAD
 
 // T: float|double   R: vectors per lane (I = R*W bodies i)   S: waves of a workgroup
 // Registers and occupancy: up to R = 4 vectors per lane (fp32: eight bodies i) fit 128 VGPRs -> four waves per SIMD.  R = 8 (round 4:
@@ -437,7 +412,16 @@ template <typename T> hipError_t launch_pair(const Shard<T>& s, const PairPlan& 
     a.self_first = 0, a.self_origin = 0, a.self_plane = npad, a.react_origin = 0, a.react_plane = npad;
     a.eps2 = s.eps2;
     const PairGeom g{p.vectors_per_lane, p.waves, p.splits};
-    if (const auto err = launch_pair_tile<T>(a, g, stream, prepare_only); err != hipSuccess || prepare_only) return err;
+    // the headline geometry has a forces kernel of its own (nbody_pair_lead.hip); a prepared step arms pair_forces too: words for
+    // pair_forces_clocked may be lent between the preparation and a launch
+    const bool lead = !NB_PAIR_VARIANT_BUILD && pair_lead_takes(a, g);
+    if (lead) {
+        if (const auto err = launch_pair_lead(a, stream, prepare_only); err != hipSuccess) return err;
+    }
+    if (!lead || prepare_only) {
+        if (const auto err = launch_pair_tile<T>(a, g, stream, prepare_only); err != hipSuccess) return err;
+    }
+    if (prepare_only) return hipSuccess;
     if (hipEvent_t probe = pair_probe_event(); probe != nullptr) {
         if (const auto err = hipEventRecord(probe, stream); err != hipSuccess) return err;
     }
