@@ -51,6 +51,8 @@ HERMITE6_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_BLOCK_LIB", os.path
 # 6th-order Hermite steps of many independent systems, a time step per system (include/nbody_hip_hermite6_ensemble.h) are a thirteenth,
 # loaded by hermite6_ensemble_lib().
 HERMITE6_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite6_ensemble.so"))
+# 6th-order block time steps of many systems in one launch per stage (include/nbody_hip_hermite6_block_ensemble.h): a library of its own
+HERMITE6_BLOCK_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_BLOCK_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite6_block_ensemble.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -534,6 +536,24 @@ HERMITE_BLOCK_ENSEMBLE_SIGNATURES = {
     "nb_hermite_block_ensemble_summary": (_ci, [_vp, _cu, _vp, _vp]),
 }
 
+# include/nbody_hip_hermite6_block_ensemble.h: exported by libnbody_hip_hermite6_block_ensemble.so, and nothing else is.  Plan and summary
+# records are the 4th-order block ensemble's.
+# positions velocities accelerations jerks snaps crackles ticks levels status workspace, workspace_bytes, N, B
+_block6_ensemble_state = [_vp] * 10 + [_sz, _cu, _cu]
+HERMITE6_BLOCK_ENSEMBLE_SIGNATURES = {
+    "nb_hermite6_block_ensemble_workspace_bytes": (_ci, [_cu, _cu, _cu, _P(_sz)]),
+    "nb_hermite6_block_ensemble_plan_f32": (_ci, [_cu, _cu, _cu, _P(HermiteBlockEnsemblePlan)]),
+    "nb_hermite6_block_ensemble_plan_f64": (_ci, [_cu, _cu, _cu, _P(HermiteBlockEnsemblePlan)]),
+    # ... softening_sq system_softening_sq params [t_stop] stream
+    "nb_hermite6_block_ensemble_init_f32": (_ci, _block6_ensemble_state + [_cf, _vp, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_ensemble_init_f64": (_ci, _block6_ensemble_state + [_cd, _vp, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_ensemble_step_f32": (_ci, _block6_ensemble_state + [_cf, _vp, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite6_block_ensemble_step_f64": (_ci, _block6_ensemble_state + [_cd, _vp, _P(HermiteBlockParams), _cd, _vp]),
+    "nb_hermite6_block_ensemble_sync_f32": (_ci, [_vp] * 10 + [_cu, _cu, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_ensemble_sync_f64": (_ci, [_vp] * 10 + [_cu, _cu, _P(HermiteBlockParams), _vp]),
+    "nb_hermite6_block_ensemble_summary": (_ci, [_vp, _cu, _vp, _vp]),
+}
+
 _lib = None
 _loaded = {}  # path -> the library at that path, its signatures set
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
@@ -602,6 +622,11 @@ def hermite6_ensemble_lib() -> ctypes.CDLL:
 def hermite_block_ensemble_lib() -> ctypes.CDLL:
     """Load libnbody_hip_hermite_block_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
     return _load(HERMITE_BLOCK_ENSEMBLE_LIB_PATH, HERMITE_BLOCK_ENSEMBLE_SIGNATURES)
+
+
+def hermite6_block_ensemble_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_hermite6_block_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    return _load(HERMITE6_BLOCK_ENSEMBLE_LIB_PATH, HERMITE6_BLOCK_ENSEMBLE_SIGNATURES)
 
 
 def hermite_block_lib() -> ctypes.CDLL:
@@ -1418,13 +1443,15 @@ class HermiteBlockEnsemble(_HermiteState):
     scalar or one value per system."""
 
     _library, _prefix = staticmethod(hermite_block_ensemble_lib), "nb_hermite_block_ensemble_"
+    _query = staticmethod(hermite_block_ensemble_workspace_bytes)
+    _default_params = (0.02, 0.01, 0.125, 30, 0)
 
     def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, params=None, softening_sq=None):
         super().__init__(dtype)
         self.num_bodies, self.num_systems = int(num_bodies), int(num_systems)
-        self.params = HermiteBlockParams(0.02, 0.01, 0.125, 30, 0) if params is None else params
+        self.params = HermiteBlockParams(*self._default_params) if params is None else params
         self.tick = float(self.params.dt_max) * 2.0 ** -int(self.params.max_level)
-        self._workspace_bytes = hermite_block_ensemble_workspace_bytes(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
+        self._workspace_bytes = self._query(self.num_bodies, self.num_systems, self.dtype)  # refuses the sizes the step refuses
         self.shape = (self.num_systems, self.num_bodies, 4)
         count = self.num_bodies * self.num_systems
         nbytes = 4 * count * self.dtype.itemsize
@@ -1453,7 +1480,7 @@ class HermiteBlockEnsemble(_HermiteState):
     def summary(self, stream=None) -> HermiteBlockEnsembleSummary:
         """the status records folded on the device (one launch), then 64 bytes read"""
         out = HermiteBlockEnsembleSummary()
-        check(hermite_block_ensemble_lib().nb_hermite_block_ensemble_summary(self._status.ptr, self.num_systems, self._summary.ptr, stream), "nb_hermite_block_ensemble_summary")
+        check(getattr(self._library(), self._prefix + "summary")(self._status.ptr, self.num_systems, self._summary.ptr, stream), self._prefix + "summary")
         check(lib().nb_d2h(ctypes.byref(out), self._summary.ptr, ctypes.sizeof(out), stream), "nb_d2h(summary)")
         return out
 
@@ -1494,6 +1521,51 @@ class HermiteBlockEnsemble(_HermiteState):
 
     def get_levels(self) -> np.ndarray:
         return self._levels.download(np.empty(self.shape[:2], dtype=np.int32))
+
+
+def hermite6_block_ensemble_plan(num_bodies: int, num_systems: int, num_active: int, dtype=np.float32) -> HermiteBlockEnsemblePlan:
+    """nb_hermite6_block_ensemble_plan_*: the solo geometry of a 6th-order block step of `num_active` of `num_bodies` bodies, and the grids of `num_systems` systems"""
+    return _plan(hermite6_block_ensemble_lib, "hermite6_block_ensemble", HermiteBlockEnsemblePlan, dtype, num_bodies, num_systems, num_active)
+
+
+def hermite6_block_ensemble_workspace_bytes(num_bodies: int, num_systems: int, dtype=np.float32) -> int:
+    return _query_workspace_bytes(hermite6_block_ensemble_lib, "hermite6_block_ensemble", dtype, num_bodies, num_systems)
+
+
+class Hermite6BlockEnsemble(HermiteBlockEnsemble):
+    """B independent systems of N bodies on the device, each stepped by the 6th-order Hermite scheme with block time steps of
+    include/nbody_hip_hermite6_block.h, all of them in the launches of one call (include/nbody_hip_hermite6_block_ensemble.h).
+
+    HermiteBlockEnsemble's arrays and methods plus the snaps and crackles.  `params` defaults to Hermite6BlockSystem's: eta 0.2 (inside
+    the root of dt_A; it does what eta = 0.02 does in the 4th-order scheme), eta_start 0.01, dt_max 0.125, 30 levels."""
+
+    _library, _prefix = staticmethod(hermite6_block_ensemble_lib), "nb_hermite6_block_ensemble_"
+    _query = staticmethod(hermite6_block_ensemble_workspace_bytes)
+    _default_params = (0.2, 0.01, 0.125, 30, 0)
+
+    def __init__(self, num_bodies: int, num_systems: int, dtype=np.float32, params=None, softening_sq=None):
+        self._snap = self._crackle = None
+        super().__init__(num_bodies, num_systems, dtype, params, softening_sq)
+        nbytes = 4 * self.num_bodies * self.num_systems * self.dtype.itemsize
+        self._snap, self._crackle = DeviceBuffer(nbytes), DeviceBuffer(nbytes)
+
+    def _buffers(self):
+        return super()._buffers() + [b for b in (self._snap, self._crackle) if b is not None]
+
+    def _state_args(self):
+        return (self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr, self._ticks.ptr, self._levels.ptr, self._status.ptr,
+                self._workspace.ptr, self._workspace_bytes, self.num_bodies, self.num_systems, *self._softening(), ctypes.byref(self.params))
+
+    def sync(self, stream=None) -> None:
+        """the synchronised snapshots, left on the device: snapshot_ptrs() for nb_energy_* (system s at byte offset s * 4 N sizeof T)"""
+        self._call("sync", self._pos_out.ptr, self._vel_out.ptr, self._pos.ptr, self._vel.ptr, self._acc.ptr, self._jerk.ptr, self._snap.ptr, self._crackle.ptr,
+                   self._ticks.ptr, self._status.ptr, self.num_bodies, self.num_systems, ctypes.byref(self.params), stream)
+
+    def get_snaps(self) -> np.ndarray:
+        return self._download(self._snap)
+
+    def get_crackles(self) -> np.ndarray:
+        return self._download(self._crackle)
 
 
 def neighbour_plan(num_bodies: int, dtype=np.float32) -> NeighbourPlan:

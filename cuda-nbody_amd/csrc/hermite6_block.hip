@@ -36,6 +36,8 @@ template <typename T> struct BodyJ {
 
 #include "hermite_block_schedule.inc"
 
+#include "hermite6_block_body.h"  // predict6_body, aarseth6_dt
+
 // the waves per SIMD hermite6_eval is compiled for (hermite6_eval.hip says why); U is hermite6_unroll_for (hermite6_kernels.h)
 template <typename T> inline constexpr int kWavesPerSimd = sizeof(T) == 8 ? 3 : 4;
 
@@ -69,18 +71,6 @@ __global__ __launch_bounds__(64 * S) __attribute__((amdgpu_waves_per_eu(kWavesPe
 }
 
 // ---- the predictor ------------------------------------------------------------------------------------------------------------------------
-
-// One body to dt: hermite6_predict's expressions (hermite6_predict.inc).  dt = 0 gives the stored bits.
-template <typename T> struct Predicted6 {
-    typename Lane<T>::vec4 x, v, a;  // {x_p, m}, {v_p, 0}, {a_p, 0}
-};
-template <typename T>
-__device__ __forceinline__ Predicted6<T> predict6_body(const typename Lane<T>::vec4& x, const typename Lane<T>::vec4& v, const typename Lane<T>::vec4& a,
-                                                       const typename Lane<T>::vec4& j, const typename Lane<T>::vec4& s, const typename Lane<T>::vec4& c, T dt) {
-    using vec4 = typename Lane<T>::vec4;
-#include "hermite6_predict.inc"
-    return {xp, vp, ap};
-}
 
 template <typename T> __global__ __launch_bounds__(256) void block6_predict_count(Block6Args<T> a, unsigned partials) {
     using vec4 = typename Lane<T>::vec4;
@@ -116,14 +106,6 @@ template <typename T> __global__ __launch_bounds__(256) void block6_predict_coun
 }
 
 // ---- the finish -----------------------------------------------------------------------------------------------------------------------
-
-// Aarseth's step with the derivatives the scheme holds, from the stored T-typed a1, j1, s1, c1, in fp64
-// (include/nbody_hip_hermite6_block.h)
-template <typename V> __device__ __forceinline__ double aarseth6_dt(const V& a1, const V& j1, const V& s1, const V& c1, double eta, double dt_max) {
-    const double n_a = norm3(a1.x, a1.y, a1.z), n_j = norm3(j1.x, j1.y, j1.z), n_s = norm3(s1.x, s1.y, s1.z), n_c = norm3(c1.x, c1.y, c1.z);
-    const double dt  = __builtin_sqrt(eta * (n_a * n_s + n_j * n_j) / (n_j * n_c + n_s * n_s));
-    return (dt == dt && dt - dt == 0) ? dt : dt_max;
-}
 
 template <typename T> __global__ __launch_bounds__(256) void hermite6_block_finish(Block6Args<T> a) {
     using vec4 = typename Lane<T>::vec4;

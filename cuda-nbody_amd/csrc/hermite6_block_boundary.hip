@@ -5,7 +5,7 @@
 #include "capi_check.h"
 #include "hermite6_block_kernels.h"
 #include "hermite6_kernels.h"
-#include "hermite_block_boundary.h"
+#include "hermite6_block_boundary.h"  // block6_params_ok: the "Range of h"
 #include "softening_floor.h"
 
 namespace {
@@ -15,17 +15,6 @@ using nb::floored, nb::Span, nb::spans_ok;
 static_assert(nb::kBlockMaxBodies <= nb::kHermite6MaxBodies, "the initial evaluation takes every N the block steps take");
 
 nb::BlockLayout layout(unsigned n, size_t size_t_of) { return nb::block_layout(n, size_t_of, 3, nb::kBlock6Sums); }  // a predicted body is three vec4
-
-// the cube of a step, as the corrector forms it in T (hh = h * h, h3 = hh * h): c1 divides by it
-template <typename T> bool cube_is_normal(double step) {
-    const T h = static_cast<T>(step), hh = h * h, h3 = hh * h;
-    return std::isnormal(h3);
-}
-
-// T: the corrector's precision.  The longest step (dt_max) and the shortest (one tick) must have normal cubes in T.
-template <typename T> bool params_ok(const nb_hermite_block_params_t* p) {
-    return nb::block_params_ok(p) && cube_is_normal<T>(std::ldexp(p->dt_max, -p->max_level)) && cube_is_normal<T>(p->dt_max);
-}
 
 template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_block_plan_t* out) {
     if (out == nullptr || !nb::block_size_ok(n) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
@@ -39,7 +28,7 @@ template <typename T> int plan_query(unsigned n, unsigned n_active, nb_hermite_b
 template <typename T>
 bool bind(nb::Block6Args<T>& a, T* pos, T* vel, T* acc, T* jerk, T* snap, T* crackle, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace,
           size_t workspace_bytes, unsigned n, const nb_hermite_block_params_t* params) {
-    if (!nb::block_size_ok(n) || !params_ok<T>(params)) return false;
+    if (!nb::block_size_ok(n) || !nb::block6_params_ok<T>(params)) return false;
     const nb::BlockLayout l = layout(n, sizeof(T));
     if (workspace_bytes < l.bytes) return false;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
@@ -96,7 +85,7 @@ int step(T* pos, T* vel, T* acc, T* jerk, T* snap, T* crackle, uint64_t* ticks, 
 template <typename T>
 int sync(T* pos_out, T* vel_out, const T* pos, const T* vel, const T* acc, const T* jerk, const T* snap, const T* crackle, const uint64_t* ticks,
          const nb_hermite_block_status_t* status, unsigned n, const nb_hermite_block_params_t* params, nb_stream_t stream) {
-    if (!nb::block_size_ok(n) || !params_ok<T>(params)) return NB_ERR_INVALID_ARGUMENT;
+    if (!nb::block_size_ok(n) || !nb::block6_params_ok<T>(params)) return NB_ERR_INVALID_ARGUMENT;
     const std::uintptr_t bodies = static_cast<std::uintptr_t>(n) * 4 * sizeof(T), al = 4 * sizeof(T);
     if (!spans_ok({{pos_out, bodies, al}, {vel_out, bodies, al}, {pos, bodies, al}, {vel, bodies, al}, {acc, bodies, al}, {jerk, bodies, al}, {snap, bodies, al},
                    {crackle, bodies, al}, {ticks, static_cast<std::uintptr_t>(n) * 8, 8}, {status, 64, 8}})) {

@@ -1,5 +1,5 @@
 // hermite6_correct.inc -- the 6th-order corrector and the new crackle of one body, as text.  One text for hermite6_eval (hermite6_eval.hip),
-// hermite6_ensemble_eval (hermite6_ensemble.hip) and hermite6_block_finish (hermite6_block.hip).  The includer has defined T, vec4, the
+// hermite6_ensemble_eval (hermite6_ensemble.hip), hermite6_block_finish (hermite6_block.hip) and hermite6_block_ensemble_finish.  The includer has defined T, vec4, the
 // body's index i, the evaluation's a1, j1, s1 (vec4 each) and two macros, which this file undefines:
 //   HERMITE6_STEP_DT          the step
 //   HERMITE6_STORED(array)    the array of the stored state -- old_pos, vel, acc, jerk, snap -- that index i counts in

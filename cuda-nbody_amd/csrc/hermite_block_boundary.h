@@ -1,5 +1,5 @@
-// hermite_block_boundary.h -- what the extern "C" boundaries of the three block-step libraries (hermite_block_capi.hip,
-// hermite6_block_boundary.hip, hermite_block_ensemble_capi.hip) share: the header's constants and records held against the kernels',
+// hermite_block_boundary.h -- what the extern "C" boundaries of the four block-step libraries (hermite_block_capi.hip,
+// hermite6_block_boundary.hip, hermite_block_ensemble_capi.hip, hermite6_block_ensemble_boundary.hip) share: the header's constants and records held against the kernels',
 // the checks of N and of the parameters, and the part of a plan that (N, num_active, precision) alone decide.  Host only.
 #pragma once
 

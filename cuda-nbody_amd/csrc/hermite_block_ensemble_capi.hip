@@ -19,6 +19,8 @@ static_assert(NB_HERMITE_BLOCK_ENSEMBLE_MAX_BODIES == nb::kEnsembleHermiteMaxBod
 static_assert(nb::kBlockEnsembleMaxBodies <= 256 * nb::kBlockThreads, "a system's counts and partial minima: one per lane of a workgroup of 256");
 static_assert(sizeof(nb_hermite_block_ensemble_summary_t) == 64 && sizeof(nb::BlockEnsembleSummary) == 64, "the summary record is 64 bytes");
 
+nb::BlockEnsembleLayout layout(unsigned n, size_t size_t_of) { return nb::block_ensemble_layout(n, size_t_of, 2, nb::kBlockSums); }  // a predicted body is two vec4
+
 // N, B and their products: every stage of every call is one launch
 template <typename T> bool size_ok(unsigned n, unsigned b) {
     if (n < 1 || n > nb::kBlockEnsembleMaxBodies || b < 1 || static_cast<unsigned long long>(n) * b > nb::kBlockEnsembleMaxTotal) return false;
@@ -32,7 +34,7 @@ template <typename T> bool size_ok(unsigned n, unsigned b) {
 
 template <typename T> int plan_query(unsigned n, unsigned b, unsigned n_active, nb_hermite_block_ensemble_plan_t* out) {
     if (out == nullptr || !size_ok<T>(n, b) || n_active < 1 || n_active > n) return NB_ERR_INVALID_ARGUMENT;
-    const nb::BlockEnsembleLayout l = nb::block_ensemble_layout(n, sizeof(T));
+    const nb::BlockEnsembleLayout l = layout(n, sizeof(T));
     nb::block_plan_fill(out, n, n_active, sizeof(T), nb::kBlockSums, sizeof(T) == 4 ? 4 : 2);
     out->step_launches     = 5;
     out->partial_offset    = l.partial;
@@ -49,7 +51,7 @@ template <typename T>
 bool bind(nb::BlockEnsembleArgs<T>& a, T* pos, T* vel, T* acc, T* jerk, uint64_t* ticks, int32_t* levels, nb_hermite_block_status_t* status, void* workspace, size_t workspace_bytes,
           unsigned n, unsigned b, T eps2, const T* system_eps2, const nb_hermite_block_params_t* params) {
     if (!size_ok<T>(n, b) || !nb::block_params_ok(params)) return false;
-    const nb::BlockEnsembleLayout l     = nb::block_ensemble_layout(n, sizeof(T));
+    const nb::BlockEnsembleLayout l     = layout(n, sizeof(T));
     const std::uintptr_t          total = static_cast<std::uintptr_t>(l.stride) * b;
     if (workspace_bytes < total) return false;
     const std::uintptr_t count = static_cast<std::uintptr_t>(n) * b, bodies = count * 4 * sizeof(T), al = 4 * sizeof(T);
@@ -115,7 +117,7 @@ extern "C" {
 int nb_hermite_block_ensemble_workspace_bytes(unsigned num_bodies, unsigned num_systems, unsigned sizeof_T, size_t* bytes) {
     if (bytes == nullptr || !nb::element_size_ok(sizeof_T)) return NB_ERR_INVALID_ARGUMENT;
     if (!(sizeof_T == 4 ? size_ok<float>(num_bodies, num_systems) : size_ok<double>(num_bodies, num_systems))) return NB_ERR_INVALID_ARGUMENT;
-    *bytes = nb::block_ensemble_layout(num_bodies, sizeof_T).stride * num_systems;
+    *bytes = layout(num_bodies, sizeof_T).stride * num_systems;
     return 0;
 }
 

@@ -37,16 +37,17 @@ inline unsigned block_ensemble_plane_groups(unsigned n, unsigned per_tile) {
 
 // ---- workspace of ONE system (byte offsets, each section on a 256-byte boundary); system s starts at s * stride ----------------------
 // The first two sections sit where block_layout (hermite_block_kernels.h) has them, so that partial_offset of the plan is the solo plan's.
+// One function for both orders, as block_layout: body_vec4 vec4 per predicted body (2; 3 with the acceleration) and `sums` partial planes.
 struct BlockEnsembleLayout {
-    size_t state8, partial, active, counts, min_part, lvl_part, ctrl, stride;
+    size_t state, partial, active, counts, min_part, lvl_part, ctrl, stride;
 };
-inline BlockEnsembleLayout block_ensemble_layout(unsigned n, size_t size_t_of) {
+inline BlockEnsembleLayout block_ensemble_layout(unsigned n, size_t size_t_of, unsigned body_vec4, unsigned sums) {
     const unsigned      per_tile = size_t_of == 4 ? 128 : 64;
     const auto          up       = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
     BlockEnsembleLayout l;
     size_t              at = 0;
-    l.state8 = at, at += up(static_cast<size_t>(n) * 8 * size_t_of);
-    l.partial = at, at += up(static_cast<size_t>(block_ensemble_plane_groups(n, per_tile)) * 6 * per_tile * size_t_of);
+    l.state = at, at += up(static_cast<size_t>(n) * 4 * body_vec4 * size_t_of);
+    l.partial = at, at += up(static_cast<size_t>(block_ensemble_plane_groups(n, per_tile)) * sums * per_tile * size_t_of);
     l.active = at, at += up(static_cast<size_t>(n) * 4);
     l.counts = at, at += up(static_cast<size_t>(block_ensemble_blocks(n)) * 4);
     l.min_part = at, at += up(static_cast<size_t>(block_ensemble_blocks(n)) * 8);

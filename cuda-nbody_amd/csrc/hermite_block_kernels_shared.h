@@ -1,5 +1,6 @@
 // hermite_block_kernels_shared.h -- the small device helpers of the block time step scheme, one text for hermite_block.hip
-// (nb_hermite_block_*), hermite6_block.hip (nb_hermite6_block_*) and hermite_block_ensemble.hip (nb_hermite_block_ensemble_*): the ticks of
+// (nb_hermite_block_*), hermite6_block.hip (nb_hermite6_block_*), hermite_block_ensemble.hip (nb_hermite_block_ensemble_*) and
+// hermite6_block_ensemble.hip (nb_hermite6_block_ensemble_*): the ticks of
 // a level, the length of a tick, the minimum / deepest-level fold and the active count of a workgroup of 256, the level a run starts at,
 // and Aarseth's step.  Included inside each translation unit's own anonymous namespace, after hermite_block_kernels.h (BlockParams).
 // (What the listings did not allow as functions is text: hermite_block_parts.inc.)

@@ -1,5 +1,5 @@
 // hermite_block_parts.inc -- what the kernels of a block step share around their own arithmetic, as TEXT included inside the kernel body, in
-// seven parts: one text for hermite_block.hip, hermite6_block.hip and hermite_block_ensemble.hip.  The includer defines ONE of the names
+// seven parts: one text for hermite_block.hip, hermite6_block.hip, hermite_block_ensemble.hip and hermite6_block_ensemble.hip.  The includer defines ONE of the names
 // below in front of each include (the fragment undefines it).  Where its records and its bodies lie it says with local names, defined
 // where its own listing wants them: between two parts where they hang on a system's slice, which the ensemble forms behind the early returns.
 //   BLOCK_PART_DECIDE        *_predict_count, behind the fold.  Requires a (p, t_stop), m (the folded MinLevel), block (the workgroup's

@@ -4,6 +4,7 @@
 #include "bodyensemblehip.hpp"
 #include "bodyensemblehip_hermite.hpp"
 #include "bodyensemblehip_hermite6.hpp"
+#include "bodyensemblehip_hermite6_block.hpp"
 #include "bodyensemblehip_hermite_block.hpp"
 #include "compute.hpp"
 #include "randomise_bodies.hpp"
@@ -80,12 +81,14 @@ template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRu
 // --integrator=hermite-block-ensemble: dt_max = dt; --t-end=T (or --steps=K: T = K dt) runs every system to the last block step not past
 // T, batches of calls and one summary between reads of 64 bytes; --benchmark times `iterations` intervals of dt after one untimed;
 // interactions are counted as the status records count them: the sum of n_act * N over the systems.  --dump: the synchronised snapshots.
-template <typename T> auto run_block_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+// --integrator=hermite6-block-ensemble is the same run on BodyEnsembleHIPHermite6Block, with --integrator=hermite6-block's name.
+template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
+    const char* const name = run.sixth ? "hermite6-block" : "hermite-block";
     const auto   n = run.num_bodies, b = run.num_systems;
     const double dt_max = static_cast<double>(static_cast<T>(run.params.time_step));
     const T      softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
     const auto   params = nb_hermite_block_params_t{run.eta, 0.01, dt_max, run.levels, 0};
-    auto         ensemble = BodyEnsembleHIPHermiteBlock<T>(n, b, softening_sq, params);
+    auto         ensemble = Ensemble(n, b, softening_sq, params);
     ensemble.set_state(pos, vel);
     const auto report = [&](const char* what, const nb_hermite_block_ensemble_summary_t& from, const nb_hermite_block_ensemble_summary_t& to) {
         const auto   body_steps  = to.body_steps - from.body_steps;
@@ -103,7 +106,7 @@ template <typename T> auto run_block_typed(const EnsembleRun& run, std::vector<T
         stop.synchronize();
         const float  milliseconds = HipEvent::elapsed_ms(begin, stop);
         const double interactions = static_cast<double>(end.body_steps - warm.body_steps) * static_cast<double>(n);
-        std::printf("%zu bodies x %zu systems, hermite-block integrator, total time for %d intervals of dt_max: %s ms\n", n, b, run.iterations, text::width3(milliseconds).c_str());
+        std::printf("%zu bodies x %zu systems, %s integrator, total time for %d intervals of dt_max: %s ms\n", n, b, name, run.iterations, text::width3(milliseconds).c_str());
         std::printf("= %s ms per interval\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
         report("= ", warm, end);
         std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
@@ -121,7 +124,7 @@ template <typename T> auto run_block_typed(const EnsembleRun& run, std::vector<T
     auto steps = std::vector<unsigned long long>();
     for (const auto& status : ensemble.statuses()) steps.push_back(status.block_steps);
     std::sort(steps.begin(), steps.end());
-    std::printf("%zu bodies x %zu systems, hermite-block integrator, eta %g, %d levels, to t = %g: %u systems stopped\n", n, b, run.eta, run.levels, t_end, end.stopped);
+    std::printf("%zu bodies x %zu systems, %s integrator, eta %g, %d levels, to t = %g: %u systems stopped\n", n, b, name, run.eta, run.levels, t_end, end.stopped);
     std::printf("block steps per system: fewest %llu, median %llu, most %llu\n", steps.front(), steps[steps.size() / 2], steps.back());
     report("", none, end);
 }
@@ -144,7 +147,7 @@ template <typename T> auto run_typed(const EnsembleRun& run) -> void {
         }
     }
     if (run.block) {
-        run_block_typed<T>(run, pos, vel);
+        if (run.sixth) run_block_typed<T, BodyEnsembleHIPHermite6Block<T>>(run, pos, vel); else run_block_typed<T, BodyEnsembleHIPHermiteBlock<T>>(run, pos, vel);
         return;
     }
     if (run.hermite) {

@@ -15,6 +15,7 @@
 //                     --integrator=hermite-ensemble --systems=<B> (... of B systems, a time step per system: libnbody_hip_hermite_ensemble.so)
 //                     --integrator=hermite-block-ensemble --systems=<B> (block time steps of B systems: libnbody_hip_hermite_block_ensemble.so)
 //                     --integrator=hermite6-ensemble --systems=<B> (6th-order steps of B systems, a time step per system: libnbody_hip_hermite6_ensemble.so)
+//                     --integrator=hermite6-block-ensemble --systems=<B> (6th-order block time steps of B systems: libnbody_hip_hermite6_block_ensemble.so)
 #include "ensemble_cli.hpp"
 #include "hermite_cli.hpp"
 #include "../../include/nbody_hip_hermite.h"
@@ -93,6 +94,7 @@ struct Options {
     bool                  hermite_ensemble = false;  // --integrator=hermite-ensemble (with --systems)
     bool                  hermite_block_ensemble = false;  // --integrator=hermite-block-ensemble (with --systems)
     bool                  hermite6_ensemble = false;  // --integrator=hermite6-ensemble (`hermite_ensemble` is set too: its restrictions, options and messages apply)
+    bool                  hermite6_block_ensemble = false;  // --integrator=hermite6-block-ensemble (`hermite_block_ensemble` is set too: its restrictions, options and messages apply)
     std::optional<double> eta;     // --eta (hermite-block, hermite-ensemble, hermite-block-ensemble)
     std::optional<double> t_end;   // --t-end (hermite-ensemble, hermite-block-ensemble)
     std::optional<int>    levels;  // --levels (hermite-block, hermite-block-ensemble)
@@ -166,6 +168,10 @@ Options:
                               with its own time.  --t-end=T (or --steps=K: T = K * dt) runs every system to its last block step not
                               past T; --dump writes every system synchronised at its own time, in --systems' format; --benchmark
                               times intervals of dt and counts the sum of n_act * N over the systems
+  --integrator=hermite6-block-ensemble  hermite-block-ensemble's run, restrictions, --t-end, --steps, --dump and --benchmark with
+                              hermite6-block's 6th-order scheme and its --eta [0.2]; the integrator is named hermite6-block in the
+                              output.  dt and dt * 2^-levels must have normal cubes in the run's precision (single: --levels up to 36
+                              with dt 0.016, up to 31 with --demo=2's dt 0.0006)
   --integrator=hermite6-ensemble  hermite-ensemble's run, restrictions, --steps, --t-end, --dump and --benchmark with the 6th-order scheme
                               (acceleration, jerk and snap per interaction).  --eta [0.025]: a system's time step is eta times the ROOT
                               of the smallest (|a||s| + |j|^2) / (|j||c| + |s|^2) of the system, so eta sits outside the root here;
@@ -312,10 +318,11 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         } else if (name == "integrator") {
             const auto v = take_value();
             ok           = v && (*v == "euler" || *v == "hermite" || *v == "hermite6" || *v == "hermite-block" || *v == "hermite6-block" || *v == "hermite-ensemble" || *v == "hermite-block-ensemble" ||
-                            *v == "hermite6-ensemble");
+                            *v == "hermite6-ensemble" || *v == "hermite6-block-ensemble");
             if (ok) {
                 options.hermite6_ensemble = *v == "hermite6-ensemble";
-                options.hermite_ensemble = *v == "hermite-ensemble" || options.hermite6_ensemble, options.hermite_block_ensemble = *v == "hermite-block-ensemble";
+                options.hermite_ensemble = *v == "hermite-ensemble" || options.hermite6_ensemble, options.hermite6_block_ensemble = *v == "hermite6-block-ensemble";
+                options.hermite_block_ensemble = *v == "hermite-block-ensemble" || options.hermite6_block_ensemble;
                 options.hermite6_block = *v == "hermite6-block";
                 options.hermite = (*v == "hermite" || *v == "hermite6" || *v == "hermite-block" || options.hermite6_block);
                 options.hermite_block = (*v == "hermite-block" || options.hermite6_block), options.hermite6 = *v == "hermite6";
@@ -431,6 +438,18 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         if (options.mode == NB_MODE_STRICT) return error("--integrator=hermite-block-ensemble has no strict mode: there is no CPU reference arithmetic to reproduce");
         if (options.t_end && (options.benchmark || options.steps > 0)) return error("--t-end cannot be combined with --benchmark or --steps (it runs every system to that time)");
     }
+    if (options.hermite6_block_ensemble) {
+        // the "Range of h" of nbody_hip_hermite6_block.h: the corrector divides by the cube of a step, formed in the run's precision
+        const double dt_max = static_cast<double>(Compute::demo_params[options.demo.value_or(0)].time_step);
+        const auto   cube_is_normal = [&](double step) {
+            if (options.fp64) return std::isnormal(step * step * step);
+            const float h = static_cast<float>(step), hh = h * h;
+            return std::isnormal(hh * h);
+        };
+        if (!cube_is_normal(dt_max) || !cube_is_normal(std::ldexp(dt_max, -options.levels.value_or(30)))) {
+            return error("--integrator=hermite6-block-ensemble: dt * 2^-levels must have a normal cube in the run's precision (fewer --levels, or --fp64)");
+        }
+    }
     if (options.t_end && !options.hermite_ensemble && !options.hermite_block_ensemble) return error("--t-end belongs to --integrator=hermite-ensemble");
 
     // (--eta is hermite-ensemble's too, and both are hermite-block-ensemble's; the message is the one the block integrator's users know)
@@ -493,8 +512,8 @@ auto main(int argc, char** argv) -> int {
             run.dump        = cmd_options.dump;
             run.hermite     = cmd_options.hermite_ensemble;
             run.t_end       = cmd_options.t_end.value_or(0.0);
-            run.sixth       = cmd_options.hermite6_ensemble;
-            run.eta         = cmd_options.eta.value_or(run.sixth ? kHermite6EnsembleEta : run.eta);
+            run.sixth       = cmd_options.hermite6_ensemble || cmd_options.hermite6_block_ensemble;
+            run.eta         = cmd_options.eta.value_or(cmd_options.hermite6_ensemble ? kHermite6EnsembleEta : cmd_options.hermite6_block_ensemble ? 0.2 : run.eta);
             run.block       = cmd_options.hermite_block_ensemble;
             run.levels      = cmd_options.levels.value_or(run.levels);
             run_ensemble(run);

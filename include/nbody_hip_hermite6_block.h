@@ -93,8 +93,8 @@
  *
  * Limits.  1 <= N <= 2^24 (NB_HERMITE_BLOCK_MAX_BODIES).  Body indices are 32-bit, byte offsets 64-bit.
  *
- * Not built: block time steps of many systems with this scheme (nbody_hip_hermite6_ensemble.h steps many systems with a time step per
- * SYSTEM, and its evaluation is what such a library would start from); a pairwise or sharded form.
+ * Not built here: block time steps of many systems with this scheme are nbody_hip_hermite6_block_ensemble.h, which takes this library's
+ * step per system, bit for bit.  Not built: a pairwise or sharded form.
  *
  * Errors.  NB_ERR_INVALID_ARGUMENT, returned before any HIP call, for: a null pointer; N (or num_active) out of range; an array not
  * aligned to 4*sizeof(T) (ticks, status: 8; levels: 4; workspace: 32); workspace_bytes too small; any two arrays of a call

@@ -88,8 +88,9 @@
  * (NB_HERMITE_ENSEMBLE_MAX_TOTAL), and B * groups_per_system * block_threads <= 2^31, so that a call is one launch per stage.  Above
  * 65 536 bodies one system fills the chip by itself: nb_hermite6_step_* is the call there.
  *
- * Not built: 6th-order block ensembles (block time steps per system with this scheme); per-system body counts; sharded forms; several
- * tiny systems packed into one wave (N < 64 * bodies_per_lane leaves lanes idle).
+ * Not built here: 6th-order block ensembles (block time steps per system with this scheme) are nbody_hip_hermite6_block_ensemble.h, whose
+ * initial evaluation is this library's.  Not built: per-system body counts; sharded forms; several tiny systems packed into one wave
+ * (N < 64 * bodies_per_lane leaves lanes idle).
  *
  * Errors.  NB_ERR_INVALID_ARGUMENT, returned before any HIP call, for: a null pointer (but the optional ones); N, B or their products
  * out of range; an array, a parameter array of step or the workspace not aligned to 4*sizeof(T) (system_softening_sq, dt_out:
