@@ -1,13 +1,15 @@
-// bodyensemblehip_hermite_block.hpp -- BodyEnsembleHIPHermiteBlock<T>: B independent systems of N bodies on the device, each stepped by
-// the Hermite scheme with block time steps, all of them in the launches of one call (nb_hermite_block_ensemble_*,
-// include/nbody_hip_hermite_block_ensemble.h, libnbody_hip_hermite_block_ensemble.so).  The state (positions, velocities, accelerations,
-// jerks, ticks, levels; system s holds bodies [s*N, (s+1)*N)), one status record per system, the summary record, the workspace and a
+// bodyensemblehip_hermite_block.hpp -- BodyEnsembleHIPHermiteBlockOrder<T, Order>: B independent systems of N bodies on the device, each
+// stepped by the Hermite scheme with block time steps, all of them in the launches of one call: at 4th order nb_hermite_block_ensemble_*
+// (include/nbody_hip_hermite_block_ensemble.h, libnbody_hip_hermite_block_ensemble.so), at 6th order nb_hermite6_block_ensemble_*
+// (include/nbody_hip_hermite6_block_ensemble.h, libnbody_hip_hermite6_block_ensemble.so); BodyEnsembleHIPHermiteBlock<T> and
+// BodyEnsembleHIPHermite6Block<T> name the two.  The state (positions, velocities, accelerations, jerks, at 6th order snaps and crackles,
+// ticks, levels; system s holds bodies [s*N, (s+1)*N)), one status record per system, the summary record, the workspace and a
 // synchronised snapshot are DeviceArrays (a device without room throws DeviceBadAlloc).  A refused call throws std::runtime_error
 // carrying the nb_error_string name.
 #pragma once
 
-#include "../../include/nbody_hip_hermite_block_ensemble.h"
 #include "device_array.hpp"
+#include "hermite_calls.hpp"
 
 #include <concepts>
 #include <cstddef>
@@ -15,18 +17,24 @@
 #include <span>
 #include <vector>
 
-template <std::floating_point T> class BodyEnsembleHIPHermiteBlock {
+template <std::floating_point T, int Order> class BodyEnsembleHIPHermiteBlockOrder {
+    using Calls = HermiteBlockEnsembleCalls<T, Order>;
+
  public:
-    BodyEnsembleHIPHermiteBlock(std::size_t num_bodies, std::size_t num_systems, T softening_sq, const nb_hermite_block_params_t& params)
+    BodyEnsembleHIPHermiteBlockOrder(std::size_t num_bodies, std::size_t num_systems, T softening_sq, const nb_hermite_block_params_t& params)
         : num_bodies_(num_bodies), num_systems_(num_systems), softening_sq_(softening_sq), params_(params) {
         // the sizes the step refuses are refused here, before anything is allocated
         const bool fits = num_bodies <= 0xFFFFFFFFu && num_systems <= 0xFFFFFFFFu;
-        hip_check(fits ? nb_hermite_block_ensemble_workspace_bytes(n(), b(), sizeof(T), &workspace_bytes_) : NB_ERR_INVALID_ARGUMENT, "nb_hermite_block_ensemble_workspace_bytes");
+        hip_check(fits ? Calls::workspace_bytes.fn(n(), b(), sizeof(T), &workspace_bytes_) : NB_ERR_INVALID_ARGUMENT, Calls::workspace_bytes.name);
         const auto bodies = num_bodies * num_systems;
-        pos_       = DeviceArray<T>(4 * bodies);
-        vel_       = DeviceArray<T>(4 * bodies);
-        acc_       = DeviceArray<T>(4 * bodies);
-        jerk_      = DeviceArray<T>(4 * bodies);
+        pos_  = DeviceArray<T>(4 * bodies);
+        vel_  = DeviceArray<T>(4 * bodies);
+        acc_  = DeviceArray<T>(4 * bodies);
+        jerk_ = DeviceArray<T>(4 * bodies);
+        if constexpr (Order == 6) {
+            snap_    = DeviceArray<T>(4 * bodies);
+            crackle_ = DeviceArray<T>(4 * bodies);
+        }
         pos_out_   = DeviceArray<T>(4 * bodies);
         vel_out_   = DeviceArray<T>(4 * bodies);
         ticks_     = DeviceArray<std::uint64_t>(bodies);
@@ -43,31 +51,29 @@ template <std::floating_point T> class BodyEnsembleHIPHermiteBlock {
     auto set_state(std::span<const T> positions, std::span<const T> velocities) -> void {
         pos_.upload(positions);
         vel_.upload(velocities);
-        if constexpr (sizeof(T) == 4) {
-            hip_check(nb_hermite_block_ensemble_init_f32(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_,
-                                                         n(), b(), softening_sq_, nullptr, &params_, nullptr), "nb_hermite_block_ensemble_init");
+        if constexpr (Order == 6) {
+            hip_check(Calls::init.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), snap_.data(), crackle_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(),
+                                     workspace_bytes_, n(), b(), softening_sq_, nullptr, &params_, nullptr), Calls::init.name);
         } else {
-            hip_check(nb_hermite_block_ensemble_init_f64(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_,
-                                                         n(), b(), softening_sq_, nullptr, &params_, nullptr), "nb_hermite_block_ensemble_init");
+            hip_check(Calls::init.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n(), b(),
+                                     softening_sq_, nullptr, &params_, nullptr), Calls::init.name);
         }
     }
 
     // one block step of every system whose next one does not pass t_stop
     auto step(double t_stop, nb_stream_t stream = nullptr) -> void {
-        int status;
-        if constexpr (sizeof(T) == 4) {
-            status = nb_hermite_block_ensemble_step_f32(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_,
-                                                        n(), b(), softening_sq_, nullptr, &params_, t_stop, stream);
+        if constexpr (Order == 6) {
+            hip_check(Calls::step.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), snap_.data(), crackle_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(),
+                                     workspace_bytes_, n(), b(), softening_sq_, nullptr, &params_, t_stop, stream), Calls::step.name);
         } else {
-            status = nb_hermite_block_ensemble_step_f64(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_,
-                                                        n(), b(), softening_sq_, nullptr, &params_, t_stop, stream);
+            hip_check(Calls::step.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n(), b(),
+                                     softening_sq_, nullptr, &params_, t_stop, stream), Calls::step.name);
         }
-        hip_check(status, "nb_hermite_block_ensemble_step");
     }
 
     // the status records folded on the device, then 64 bytes read (waits for the calls before it)
     auto summary(nb_stream_t stream = nullptr) -> nb_hermite_block_ensemble_summary_t {
-        hip_check(nb_hermite_block_ensemble_summary(status_.data(), b(), summary_.data(), stream), "nb_hermite_block_ensemble_summary");
+        hip_check(Calls::summary.fn(status_.data(), b(), summary_.data(), stream), Calls::summary.name);
         nb_hermite_block_ensemble_summary_t out{};
         summary_.download(std::span<nb_hermite_block_ensemble_summary_t>(&out, 1));
         return out;
@@ -89,13 +95,13 @@ template <std::floating_point T> class BodyEnsembleHIPHermiteBlock {
 
     // every body predicted to its system's status time -> get_positions(), get_velocities()
     auto sync(nb_stream_t stream = nullptr) -> void {
-        int status;
-        if constexpr (sizeof(T) == 4) {
-            status = nb_hermite_block_ensemble_sync_f32(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), status_.data(), n(), b(), &params_, stream);
+        if constexpr (Order == 6) {
+            hip_check(Calls::sync.fn(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), snap_.data(), crackle_.data(), ticks_.data(), status_.data(), n(), b(),
+                                     &params_, stream), Calls::sync.name);
         } else {
-            status = nb_hermite_block_ensemble_sync_f64(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), status_.data(), n(), b(), &params_, stream);
+            hip_check(Calls::sync.fn(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), status_.data(), n(), b(), &params_, stream),
+                      Calls::sync.name);
         }
-        hip_check(status, "nb_hermite_block_ensemble_sync");
     }
     auto get_positions(std::span<T> out) const -> void { pos_out_.download(out); }
     auto get_velocities(std::span<T> out) const -> void { vel_out_.download(out); }
@@ -107,10 +113,13 @@ template <std::floating_point T> class BodyEnsembleHIPHermiteBlock {
     T                                                softening_sq_;
     nb_hermite_block_params_t                        params_;
     std::size_t                                      workspace_bytes_ = 0;
-    DeviceArray<T>                                   pos_, vel_, acc_, jerk_, pos_out_, vel_out_;
+    DeviceArray<T>                                   pos_, vel_, acc_, jerk_, snap_, crackle_, pos_out_, vel_out_;  // (snap_ and crackle_ stay empty at 4th order)
     DeviceArray<std::uint64_t>                       ticks_;
     DeviceArray<std::int32_t>                        levels_;
     DeviceArray<nb_hermite_block_status_t>           status_;
     DeviceArray<nb_hermite_block_ensemble_summary_t> summary_;
     DeviceArray<unsigned char>                       workspace_;
 };
+
+template <std::floating_point T> using BodyEnsembleHIPHermiteBlock  = BodyEnsembleHIPHermiteBlockOrder<T, 4>;
+template <std::floating_point T> using BodyEnsembleHIPHermite6Block = BodyEnsembleHIPHermiteBlockOrder<T, 6>;

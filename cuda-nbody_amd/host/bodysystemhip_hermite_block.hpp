@@ -1,27 +1,36 @@
-// bodysystemhip_hermite_block.hpp -- BodySystemHIPHermiteBlock<T>: one system of N bodies on the device, stepped by the Hermite scheme
-// with block time steps of nb_hermite_block_* (include/nbody_hip_hermite_block.h, libnbody_hip_hermite_block.so).  The state
-// (positions, velocities, accelerations, jerks, ticks, levels), the status record, the workspace and a synchronised snapshot are
-// DeviceArrays (a device without room throws DeviceBadAlloc).  A refused call throws std::runtime_error carrying the nb_error_string name.
+// bodysystemhip_hermite_block.hpp -- BodySystemHIPHermiteBlockOrder<T, Order>: one system of N bodies on the device, stepped by the
+// Hermite scheme with block time steps, at 4th order by nb_hermite_block_* (include/nbody_hip_hermite_block.h,
+// libnbody_hip_hermite_block.so), at 6th order by nb_hermite6_block_* (include/nbody_hip_hermite6_block.h,
+// libnbody_hip_hermite6_block.so); BodySystemHIPHermiteBlock<T> and BodySystemHIPHermite6Block<T> name the two.  The state (positions,
+// velocities, accelerations, jerks, at 6th order snaps and crackles, ticks, levels), the status record, the workspace and a synchronised
+// snapshot are DeviceArrays (a device without room throws DeviceBadAlloc).  A refused call throws std::runtime_error carrying the
+// nb_error_string name.
 #pragma once
 
-#include "../../include/nbody_hip_hermite_block.h"
 #include "device_array.hpp"
+#include "hermite_calls.hpp"
 
 #include <concepts>
 #include <cstddef>
 #include <cstdint>
 #include <span>
 
-template <std::floating_point T> class BodySystemHIPHermiteBlock {
+template <std::floating_point T, int Order> class BodySystemHIPHermiteBlockOrder {
+    using Calls = HermiteBlockCalls<T, Order>;
+
  public:
-    BodySystemHIPHermiteBlock(std::size_t num_bodies, T softening_sq, const nb_hermite_block_params_t& params) : num_bodies_(num_bodies), softening_sq_(softening_sq), params_(params) {
+    BodySystemHIPHermiteBlockOrder(std::size_t num_bodies, T softening_sq, const nb_hermite_block_params_t& params) : num_bodies_(num_bodies), softening_sq_(softening_sq), params_(params) {
         // the sizes the step refuses are refused here, before anything is allocated
-        hip_check(num_bodies <= 0xFFFFFFFFu ? nb_hermite_block_workspace_bytes(static_cast<unsigned>(num_bodies), sizeof(T), &workspace_bytes_) : NB_ERR_INVALID_ARGUMENT,
-                  "nb_hermite_block_workspace_bytes");
-        pos_       = DeviceArray<T>(4 * num_bodies);
-        vel_       = DeviceArray<T>(4 * num_bodies);
-        acc_       = DeviceArray<T>(4 * num_bodies);
-        jerk_      = DeviceArray<T>(4 * num_bodies);
+        hip_check(num_bodies <= 0xFFFFFFFFu ? Calls::workspace_bytes.fn(static_cast<unsigned>(num_bodies), sizeof(T), &workspace_bytes_) : NB_ERR_INVALID_ARGUMENT,
+                  Calls::workspace_bytes.name);
+        pos_  = DeviceArray<T>(4 * num_bodies);
+        vel_  = DeviceArray<T>(4 * num_bodies);
+        acc_  = DeviceArray<T>(4 * num_bodies);
+        jerk_ = DeviceArray<T>(4 * num_bodies);
+        if constexpr (Order == 6) {
+            snap_    = DeviceArray<T>(4 * num_bodies);
+            crackle_ = DeviceArray<T>(4 * num_bodies);
+        }
         pos_out_   = DeviceArray<T>(4 * num_bodies);
         vel_out_   = DeviceArray<T>(4 * num_bodies);
         ticks_     = DeviceArray<std::uint64_t>(num_bodies);
@@ -40,27 +49,25 @@ template <std::floating_point T> class BodySystemHIPHermiteBlock {
         pos_.upload(positions);
         vel_.upload(velocities);
         const auto n = static_cast<unsigned>(num_bodies_);
-        if constexpr (sizeof(T) == 4) {
-            hip_check(nb_hermite_block_init_f32(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n,
-                                                softening_sq_, &params_, nullptr), "nb_hermite_block_init");
+        if constexpr (Order == 6) {
+            hip_check(Calls::init.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), snap_.data(), crackle_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(),
+                                     workspace_bytes_, n, softening_sq_, &params_, nullptr), Calls::init.name);
         } else {
-            hip_check(nb_hermite_block_init_f64(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n,
-                                                softening_sq_, &params_, nullptr), "nb_hermite_block_init");
+            hip_check(Calls::init.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n, softening_sq_,
+                                     &params_, nullptr), Calls::init.name);
         }
     }
 
     // one block step, or nothing but the flag when it would pass t_stop
     auto step(double t_stop, nb_stream_t stream = nullptr) -> void {
         const auto n = static_cast<unsigned>(num_bodies_);
-        int        status;
-        if constexpr (sizeof(T) == 4) {
-            status = nb_hermite_block_step_f32(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n,
-                                               softening_sq_, &params_, t_stop, stream);
+        if constexpr (Order == 6) {
+            hip_check(Calls::step.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), snap_.data(), crackle_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(),
+                                     workspace_bytes_, n, softening_sq_, &params_, t_stop, stream), Calls::step.name);
         } else {
-            status = nb_hermite_block_step_f64(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n,
-                                               softening_sq_, &params_, t_stop, stream);
+            hip_check(Calls::step.fn(pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), levels_.data(), status_.data(), workspace_.data(), workspace_bytes_, n, softening_sq_,
+                                     &params_, t_stop, stream), Calls::step.name);
         }
-        hip_check(status, "nb_hermite_block_step");
     }
 
     auto status() const -> nb_hermite_block_status_t {
@@ -81,13 +88,12 @@ template <std::floating_point T> class BodySystemHIPHermiteBlock {
     // every body predicted to the status time -> positions(), velocities()
     auto sync(nb_stream_t stream = nullptr) -> void {
         const auto n = static_cast<unsigned>(num_bodies_);
-        int        status;
-        if constexpr (sizeof(T) == 4) {
-            status = nb_hermite_block_sync_f32(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), status_.data(), n, &params_, stream);
+        if constexpr (Order == 6) {
+            hip_check(Calls::sync.fn(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), snap_.data(), crackle_.data(), ticks_.data(), status_.data(), n,
+                                     &params_, stream), Calls::sync.name);
         } else {
-            status = nb_hermite_block_sync_f64(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), status_.data(), n, &params_, stream);
+            hip_check(Calls::sync.fn(pos_out_.data(), vel_out_.data(), pos_.data(), vel_.data(), acc_.data(), jerk_.data(), ticks_.data(), status_.data(), n, &params_, stream), Calls::sync.name);
         }
-        hip_check(status, "nb_hermite_block_sync");
     }
     auto get_positions(std::span<T> out) const -> void { pos_out_.download(out); }
     auto get_velocities(std::span<T> out) const -> void { vel_out_.download(out); }
@@ -97,9 +103,12 @@ template <std::floating_point T> class BodySystemHIPHermiteBlock {
     T                                      softening_sq_;
     nb_hermite_block_params_t              params_;
     std::size_t                            workspace_bytes_ = 0;
-    DeviceArray<T>                         pos_, vel_, acc_, jerk_, pos_out_, vel_out_;
+    DeviceArray<T>                         pos_, vel_, acc_, jerk_, snap_, crackle_, pos_out_, vel_out_;  // (snap_ and crackle_ stay empty at 4th order)
     DeviceArray<std::uint64_t>             ticks_;
     DeviceArray<std::int32_t>              levels_;
     DeviceArray<nb_hermite_block_status_t> status_;
     DeviceArray<unsigned char>             workspace_;
 };
+
+template <std::floating_point T> using BodySystemHIPHermiteBlock  = BodySystemHIPHermiteBlockOrder<T, 4>;
+template <std::floating_point T> using BodySystemHIPHermite6Block = BodySystemHIPHermiteBlockOrder<T, 6>;

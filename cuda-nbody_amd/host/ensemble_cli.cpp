@@ -3,31 +3,19 @@
 
 #include "bodyensemblehip.hpp"
 #include "bodyensemblehip_hermite.hpp"
-#include "bodyensemblehip_hermite6.hpp"
-#include "bodyensemblehip_hermite6_block.hpp"
 #include "bodyensemblehip_hermite_block.hpp"
-#include "compute.hpp"
-#include "randomise_bodies.hpp"
+#include "cli_common.hpp"
 #include "text.hpp"
 
 #include <algorithm>
 #include <cstdio>
-#include <fstream>
-#include <stdexcept>
 #include <vector>
 
 namespace {
 
-template <typename T> auto write_dump(const EnsembleRun& run, const std::vector<T>& pos, const std::vector<T>& vel) -> void {
-    auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
-    if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
-    out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
-    out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
-}
-
 // --integrator=hermite-ensemble: --steps=K takes K fixed steps of --integrator=hermite's dt; --t-end runs the adaptive form, batches of calls
 // between reads of the 64-byte status record; --benchmark times `iterations` fixed steps after one untimed, B N^2 interactions per step.
-// --integrator=hermite6-ensemble is the same run on BodyEnsembleHIPHermite6, with --integrator=hermite6's name and interaction count.
+// --integrator=hermite6-ensemble is the same run at Order 6, with --integrator=hermite6's name and interaction count.
 template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
     const char* const name = run.sixth ? "hermite6" : "hermite";
     const auto n = run.num_bodies, b = run.num_systems;
@@ -74,14 +62,14 @@ template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRu
     if (!run.dump.empty()) {
         ensemble.get_positions(pos);
         ensemble.get_velocities(vel);
-        write_dump<T>(run, pos, vel);
+        write_dump<T>(run.dump, pos, vel);
     }
 }
 
 // --integrator=hermite-block-ensemble: dt_max = dt; --t-end=T (or --steps=K: T = K dt) runs every system to the last block step not past
 // T, batches of calls and one summary between reads of 64 bytes; --benchmark times `iterations` intervals of dt after one untimed;
 // interactions are counted as the status records count them: the sum of n_act * N over the systems.  --dump: the synchronised snapshots.
-// --integrator=hermite6-block-ensemble is the same run on BodyEnsembleHIPHermite6Block, with --integrator=hermite6-block's name.
+// --integrator=hermite6-block-ensemble is the same run at Order 6, with --integrator=hermite6-block's name.
 template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
     const char* const name = run.sixth ? "hermite6-block" : "hermite-block";
     const auto   n = run.num_bodies, b = run.num_systems;
@@ -119,7 +107,7 @@ template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun&
         ensemble.sync();
         ensemble.get_positions(pos);
         ensemble.get_velocities(vel);
-        write_dump<T>(run, pos, vel);
+        write_dump<T>(run.dump, pos, vel);
     }
     auto steps = std::vector<unsigned long long>();
     for (const auto& status : ensemble.statuses()) steps.push_back(status.block_steps);
@@ -129,31 +117,9 @@ template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun&
     report("", none, end);
 }
 
-template <typename T> auto run_typed(const EnsembleRun& run) -> void {
+// --systems without a Hermite integrator: BodyEnsembleHIP's leapfrog steps
+template <typename T> auto run_plain_typed(const EnsembleRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
     const auto n = run.num_bodies, b = run.num_systems;
-    std::vector<T> pos(4 * n * b), vel(4 * n * b);
-    {
-        // the single-system start-up state (Compute's constructor): an fp32 and an fp64 system reset with demo row 0's scales, then
-        // the active precision with the N-scaled ones -- the third segment is system 0, the next draws are systems 1 .. B-1
-        std::vector<float>  p32(4 * n), v32(4 * n);
-        std::vector<double> p64(4 * n), v64(4 * n);
-        const auto demo0 = Compute::demo_params[0];
-        randomise_bodies<float>(NBodyConfig::NBODY_CONFIG_SHELL, p32, v32, demo0.cluster_scale, demo0.velocity_scale);
-        randomise_bodies<double>(NBodyConfig::NBODY_CONFIG_SHELL, p64, v64, demo0.cluster_scale, demo0.velocity_scale);
-        auto scaled = demo0;
-        Compute::scale_params_for(n, scaled);
-        for (std::size_t s = 0; s < b; ++s) {
-            randomise_bodies<T>(run.config, std::span<T>(pos).subspan(4 * n * s, 4 * n), std::span<T>(vel).subspan(4 * n * s, 4 * n), scaled.cluster_scale, scaled.velocity_scale);
-        }
-    }
-    if (run.block) {
-        if (run.sixth) run_block_typed<T, BodyEnsembleHIPHermite6Block<T>>(run, pos, vel); else run_block_typed<T, BodyEnsembleHIPHermiteBlock<T>>(run, pos, vel);
-        return;
-    }
-    if (run.hermite) {
-        if (run.sixth) run_hermite_typed<T, BodyEnsembleHIPHermite6<T>>(run, pos, vel); else run_hermite_typed<T, BodyEnsembleHIPHermite<T>>(run, pos, vel);
-        return;
-    }
     auto ensemble = BodyEnsembleHIP<T>(n, b, run.mode);
     ensemble.set_positions(pos);
     ensemble.set_velocities(vel);
@@ -180,12 +146,23 @@ template <typename T> auto run_typed(const EnsembleRun& run) -> void {
     if (!run.dump.empty()) {
         ensemble.get_positions(pos);
         ensemble.get_velocities(vel);
-        write_dump<T>(run, pos, vel);
+        write_dump<T>(run.dump, pos, vel);
     }
 }
 
 }  // namespace
 
 auto run_ensemble(const EnsembleRun& run) -> void {
-    if (run.fp64) run_typed<double>(run); else run_typed<float>(run);
+    with_precision_and_order(run.fp64, run.sixth, [&]<typename T, int Order>() {
+        const auto n = run.num_bodies, b = run.num_systems;
+        std::vector<T> pos(4 * n * b), vel(4 * n * b);
+        startup_state<T>(run.config, n, b, pos, vel);
+        if (run.block) {
+            run_block_typed<T, BodyEnsembleHIPHermiteBlockOrder<T, Order>>(run, pos, vel);
+        } else if (run.hermite) {
+            run_hermite_typed<T, BodyEnsembleHIPHermiteOrder<T, Order>>(run, pos, vel);
+        } else {
+            run_plain_typed<T>(run, pos, vel);
+        }
+    });
 }

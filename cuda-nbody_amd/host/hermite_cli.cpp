@@ -2,20 +2,15 @@
 #include "hermite_cli.hpp"
 
 #include "bodysystemhip_hermite.hpp"
-#include "bodysystemhip_hermite6.hpp"
-#include "bodysystemhip_hermite6_block.hpp"
 #include "bodysystemhip_hermite_block.hpp"
-#include "compute.hpp"
+#include "cli_common.hpp"
 #include "field_cli.hpp"
 #include "knn_cli.hpp"
 #include "neighbour_cli.hpp"
-#include "randomise_bodies.hpp"
 #include "text.hpp"
 
 #include <cmath>
 #include <cstdio>
-#include <fstream>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -44,29 +39,55 @@ auto print_energy(const std::string& what, const nb_energy_t& e) -> void {
     std::printf("%s: kinetic=%.9g potential=%.9g total=%.9g momentum=%.9g,%.9g,%.9g", what.c_str(), e.kinetic, e.potential, e.total, e.momentum[0], e.momentum[1], e.momentum[2]);
 }
 
-// the single-system start-up state (Compute's constructor)
-template <typename T> auto startup_state(const HermiteRun& run, std::vector<T>& pos, std::vector<T>& vel) -> void {
-    const auto n = run.num_bodies;
-    {
-        // the single-system start-up state (Compute's constructor): an fp32 and an fp64 system reset with demo row 0's scales, then
-        // the active precision with the N-scaled ones
-        std::vector<float>  p32(4 * n), v32(4 * n);
-        std::vector<double> p64(4 * n), v64(4 * n);
-        const auto demo0 = Compute::demo_params[0];
-        randomise_bodies<float>(NBodyConfig::NBODY_CONFIG_SHELL, p32, v32, demo0.cluster_scale, demo0.velocity_scale);
-        randomise_bodies<double>(NBodyConfig::NBODY_CONFIG_SHELL, p64, v64, demo0.cluster_scale, demo0.velocity_scale);
-        auto scaled = demo0;
-        Compute::scale_params_for(n, scaled);
-        randomise_bodies<T>(run.config, pos, vel, scaled.cluster_scale, scaled.velocity_scale);
+// What a run reports besides its own lines, of the fixed-step and of the block systems alike: --energy (measured at construction, after
+// set_state, and again by energy()), --neighbours, --knn and --field of the present state.  A block system is synchronised first: each
+// report reads its snapshot.
+template <typename T, typename System> class Reports {
+ public:
+    Reports(const HermiteRun& run, System& system, std::vector<T>& pos, T softening_sq)
+        : run_(run), system_(system), pos_(pos), softening_sq_(softening_sq), measure_(run.energy && (run.benchmark || run.steps > 0)) {
+        if (!measure_) return;
+        snapshot();
+        start_ = energy_of(system_, softening_sq_);
     }
-}
+    auto energy(std::size_t steps) -> void {
+        if (!measure_) return;
+        snapshot();
+        const auto end = energy_of(system_, softening_sq_);
+        print_energy("energy start", start_);
+        std::printf("\n");
+        print_energy("energy end (" + std::to_string(steps) + " steps)", end);
+        std::printf(" relative_drift=%.9g\n", (end.total - start_.total) / std::abs(start_.total));
+    }
+    auto neighbourhood() -> void {
+        if (run_.neighbours < 0) return;
+        report_neighbours(positions(), run_.neighbours, softening_sq_);
+    }
+    auto structure() -> void {
+        if (run_.knn == 0) return;
+        report_knn(positions(), run_.knn);
+    }
+    auto field_points() -> void {
+        if (run_.field_points.empty()) return;
+        report_field(positions(), run_.field_points, softening_sq_);
+    }
 
-template <typename T> auto write_dump(const HermiteRun& run, const std::vector<T>& pos, const std::vector<T>& vel) -> void {
-    auto out = std::ofstream(run.dump, std::ios::binary | std::ios::trunc);
-    if (!out) throw std::runtime_error("cannot open dump file " + run.dump.string());
-    out.write(reinterpret_cast<const char*>(pos.data()), static_cast<std::streamsize>(pos.size() * sizeof(T)));
-    out.write(reinterpret_cast<const char*>(vel.data()), static_cast<std::streamsize>(vel.size() * sizeof(T)));
-}
+ private:
+    auto snapshot() -> void {
+        if constexpr (requires { system_.sync(); }) system_.sync();
+    }
+    auto positions() -> std::span<const T> {
+        snapshot();
+        system_.get_positions(pos_);
+        return pos_;
+    }
+    const HermiteRun& run_;
+    System&           system_;
+    std::vector<T>&   pos_;
+    T                 softening_sq_;
+    bool              measure_;
+    nb_energy_t       start_{};
+};
 
 // what --benchmark prints of a scheme: its name, the flops of one interaction as its library evaluates it, and what the interaction returns
 struct Scheme {
@@ -89,50 +110,18 @@ constexpr Scheme kHermite6Block{"hermite6-block", kHermite6.flops, kHermite6.int
 template <typename T, typename System> auto run_block_typed(const HermiteRun& run, const Scheme& scheme) -> void {
     const auto     n = run.num_bodies;
     std::vector<T> pos(4 * n), vel(4 * n);
-    startup_state<T>(run, pos, vel);
+    startup_state<T>(run.config, n, 1, pos, vel);
     const double dt_max = static_cast<double>(static_cast<T>(run.params.time_step));
     const T      softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
     const auto   params = nb_hermite_block_params_t{run.eta, 0.01, dt_max, run.levels, 0};
     auto         system = System(n, softening_sq, params);
     system.set_state(pos, vel);
-    const auto measure = run.energy && (run.benchmark || run.steps > 0);
-    nb_energy_t start{};
-    if (measure) {
-        system.sync();
-        start = energy_of(system, softening_sq);
-    }
+    auto reports = Reports<T, System>(run, system, pos, softening_sq);
     const auto report = [&](const char* what, const nb_hermite_block_status_t& from, const nb_hermite_block_status_t& to) {
         const auto   body_steps = to.body_steps - from.body_steps;
         const double evaluations = static_cast<double>(body_steps) / static_cast<double>(n);
         std::printf("%s%llu block steps, %llu body steps = %s evaluations of N^2 interactions, deepest level %d\n", what, static_cast<unsigned long long>(to.block_steps - from.block_steps),
                     static_cast<unsigned long long>(body_steps), text::width3(static_cast<float>(evaluations)).c_str(), to.deepest_level);
-    };
-    const auto report_energy = [&](std::size_t intervals) {
-        if (!measure) return;
-        system.sync();
-        const auto end = energy_of(system, softening_sq);
-        print_energy("energy start", start);
-        std::printf("\n");
-        print_energy("energy end (" + std::to_string(intervals) + " steps)", end);
-        std::printf(" relative_drift=%.9g\n", (end.total - start.total) / std::abs(start.total));
-    };
-    const auto report_neighbourhood = [&]() {  // (of the synchronised snapshot)
-        if (run.neighbours < 0) return;
-        system.sync();
-        system.get_positions(pos);
-        report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
-    };
-    const auto report_structure = [&]() {  // (of the synchronised snapshot)
-        if (run.knn == 0) return;
-        system.sync();
-        system.get_positions(pos);
-        report_knn(std::span<const T>(pos), run.knn);
-    };
-    const auto report_field_points = [&]() {  // (of the synchronised snapshot)
-        if (run.field_points.empty()) return;
-        system.sync();
-        system.get_positions(pos);
-        report_field(std::span<const T>(pos), run.field_points, softening_sq);
     };
     if (run.benchmark) {
         const auto warm = system.advance(dt_max);  // (untimed, as Compute::run_benchmark)
@@ -152,9 +141,9 @@ template <typename T, typename System> auto run_block_typed(const HermiteRun& ru
             std::printf("= %s %s-precision GFLOP/s at %d flops per %s interaction\n", text::width3(per_second * static_cast<float>(scheme.flops)).c_str(),
                         sizeof(T) == 8 ? "double" : "single", scheme.flops, scheme.interaction);
         }
-        report_energy(1 + static_cast<std::size_t>(run.iterations));
-        report_neighbourhood();
-        report_field_points();
+        reports.energy(1 + static_cast<std::size_t>(run.iterations));
+        reports.neighbourhood();
+        reports.field_points();
         return;
     }
     const auto none = system.status();
@@ -163,50 +152,25 @@ template <typename T, typename System> auto run_block_typed(const HermiteRun& ru
         system.sync();
         system.get_positions(pos);
         system.get_velocities(vel);
-        write_dump<T>(run, pos, vel);
+        write_dump<T>(run.dump, pos, vel);
     }
     report("", none, end);
-    report_energy(run.steps);
-    report_neighbourhood();
-    report_structure();
-    report_field_points();
+    reports.energy(run.steps);
+    reports.neighbourhood();
+    reports.structure();
+    reports.field_points();
 }
 
 template <typename T, typename System> auto run_typed(const HermiteRun& run, const Scheme& scheme) -> void {
     const auto     n = run.num_bodies;
     std::vector<T> pos(4 * n), vel(4 * n);
-    startup_state<T>(run, pos, vel);
+    startup_state<T>(run.config, n, 1, pos, vel);
     // BodySystemHIP's conversions: dt float -> T, softening^2 = T(s) * T(s)
     const T dt = static_cast<T>(run.params.time_step);
     const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
     auto system = System(n, softening_sq);
     system.set_state(pos, vel);
-    const auto measure = run.energy && (run.benchmark || run.steps > 0);
-    nb_energy_t start{};
-    if (measure) start = energy_of(system, softening_sq);
-    const auto report_energy = [&](std::size_t steps) {
-        if (!measure) return;
-        const auto end = energy_of(system, softening_sq);
-        print_energy("energy start", start);
-        std::printf("\n");
-        print_energy("energy end (" + std::to_string(steps) + " steps)", end);
-        std::printf(" relative_drift=%.9g\n", (end.total - start.total) / std::abs(start.total));
-    };
-    const auto report_neighbourhood = [&]() {
-        if (run.neighbours < 0) return;
-        system.get_positions(pos);
-        report_neighbours(std::span<const T>(pos), run.neighbours, softening_sq);
-    };
-    const auto report_structure = [&]() {
-        if (run.knn == 0) return;
-        system.get_positions(pos);
-        report_knn(std::span<const T>(pos), run.knn);
-    };
-    const auto report_field_points = [&]() {
-        if (run.field_points.empty()) return;
-        system.get_positions(pos);
-        report_field(std::span<const T>(pos), run.field_points, softening_sq);
-    };
+    auto reports = Reports<T, System>(run, system, pos, softening_sq);
     if (run.benchmark) {
         system.update(dt);  // (untimed, as Compute::run_benchmark)
         HipEvent begin, stop;
@@ -223,37 +187,31 @@ template <typename T, typename System> auto run_typed(const HermiteRun& run, con
         std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
         std::printf("= %s %s-precision GFLOP/s at %d flops per %s interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
                     sizeof(T) == 8 ? "double" : "single", flops, scheme.interaction);
-        report_energy(1 + static_cast<std::size_t>(run.iterations));
-        report_neighbourhood();
-        report_field_points();
+        reports.energy(1 + static_cast<std::size_t>(run.iterations));
+        reports.neighbourhood();
+        reports.field_points();
         return;
     }
     for (std::size_t s = 0; s < run.steps; ++s) system.update(dt);
     if (!run.dump.empty()) {
         system.get_positions(pos);
         system.get_velocities(vel);
-        write_dump<T>(run, pos, vel);
+        write_dump<T>(run.dump, pos, vel);
     }
-    report_energy(run.steps);
-    report_neighbourhood();
-    report_structure();
-    report_field_points();
+    reports.energy(run.steps);
+    reports.neighbourhood();
+    reports.structure();
+    reports.field_points();
 }
 
 }  // namespace
 
 auto run_hermite(const HermiteRun& run) -> void {
-    if (run.block) {
-        if (run.sixth) {
-            if (run.fp64) run_block_typed<double, BodySystemHIPHermite6Block<double>>(run, kHermite6Block); else run_block_typed<float, BodySystemHIPHermite6Block<float>>(run, kHermite6Block);
-            return;
+    with_precision_and_order(run.fp64, run.sixth, [&]<typename T, int Order>() {
+        if (run.block) {
+            run_block_typed<T, BodySystemHIPHermiteBlockOrder<T, Order>>(run, Order == 6 ? kHermite6Block : kHermiteBlock);
+        } else {
+            run_typed<T, BodySystemHIPHermiteOrder<T, Order>>(run, Order == 6 ? kHermite6 : kHermite4);
         }
-        if (run.fp64) run_block_typed<double, BodySystemHIPHermiteBlock<double>>(run, kHermiteBlock); else run_block_typed<float, BodySystemHIPHermiteBlock<float>>(run, kHermiteBlock);
-        return;
-    }
-    if (run.sixth) {
-        if (run.fp64) run_typed<double, BodySystemHIPHermite6<double>>(run, kHermite6); else run_typed<float, BodySystemHIPHermite6<float>>(run, kHermite6);
-        return;
-    }
-    if (run.fp64) run_typed<double, BodySystemHIPHermite<double>>(run, kHermite4); else run_typed<float, BodySystemHIPHermite<float>>(run, kHermite4);
+    });
 }
