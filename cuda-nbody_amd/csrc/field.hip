@@ -279,23 +279,16 @@ template <typename T, bool JERK> __global__ __launch_bounds__(256) void field_fi
     if (a.pot != nullptr) a.pot[slot] = -sum[3];
 }
 
-template <typename T, int S, bool JERK> hipError_t launch_s(const FieldArgs<T>& a, const FieldGeom& g, hipStream_t stream) {
-    (void)hipGetLastError();  // a launch reports ITS OWN error
-    hipLaunchKernelGGL((field_eval<T, S, JERK>), dim3(g.tiles * g.ranges), dim3(64 * S), 0, stream, a, g.ranges);
-    if (const auto err = hipGetLastError(); err != hipSuccess || g.ranges == 1) return err;
-    hipLaunchKernelGGL((field_finish<T, JERK>), dim3((a.m + kFieldThreads - 1) / kFieldThreads), dim3(kFieldThreads), 0, stream, a, g.ranges, g.tiles);
-    return hipGetLastError();
-}
-
 template <typename T, bool JERK> hipError_t launch_planned(const FieldArgs<T>& a, hipStream_t stream) {
     const FieldGeom g = field_geometry(a.n, a.m, 64 * Lane<T>::W);
-    switch (g.waves) {
-        case 1: return launch_s<T, 1, JERK>(a, g, stream);
-        case 2: return launch_s<T, 2, JERK>(a, g, stream);
-        case 4: return launch_s<T, 4, JERK>(a, g, stream);
-        case 8: return launch_s<T, 8, JERK>(a, g, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return with_stream_waves(g.waves, [&](auto waves) {
+        constexpr int S = decltype(waves)::value;
+        (void)hipGetLastError();  // a launch reports ITS OWN error
+        hipLaunchKernelGGL((field_eval<T, S, JERK>), dim3(g.tiles * g.ranges), dim3(64 * S), 0, stream, a, g.ranges);
+        if (const auto err = hipGetLastError(); err != hipSuccess || g.ranges == 1) return err;
+        hipLaunchKernelGGL((field_finish<T, JERK>), dim3((a.m + kFieldThreads - 1) / kFieldThreads), dim3(kFieldThreads), 0, stream, a, g.ranges, g.tiles);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace

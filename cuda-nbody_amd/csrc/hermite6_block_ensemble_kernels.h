@@ -10,8 +10,6 @@
 
 namespace nb {
 
-inline BlockEnsembleLayout block6_ensemble_layout(unsigned n, size_t size_t_of) { return block_ensemble_layout(n, size_t_of, 3, kBlock6Sums); }
-
 // The order-independent schedule kernels (hermite_block_ensemble_schedule.inc) read the base alone.
 template <typename T> struct Block6EnsembleArgs : BlockEnsembleArgs<T> {
     T *snap, *crackle;  // stored state T[4 N B]

@@ -2,7 +2,7 @@
 // of B independent systems of N bodies in one launch per stage, each system with a time step of its own.  gfx950 only; FMA contraction on.
 //
 // hermite6_ensemble_eval<T, S, STEP> is hermite6_eval (hermite6_eval.hip) per system: workgroup g works on tile g mod G of system g / G, G the
-// workgroups plan_hermite6 gives one system of N bodies, S = stream_waves(N).  What lies between a lane's bodies i and its nine sums is the
+// workgroups plan_stream (wave_stream.h) gives one system of N bodies, S = stream_waves(N).  What lies between a lane's bodies i and its nine sums is the
 // same TEXT (hermite_stream.inc with HERMITE_STREAM_SUMS 9 and hermite6_interaction.inc, a body j of three adjacent vec4), and so are the
 // predictor (hermite6_predict.inc), the corrector with the new crackle (hermite6_correct.inc), the pack (hermite6_pack.inc) and the ratio
 // behind the time step (hermite6_ratio.h): a system's sums are formed in the order the solo kernel forms them and its bits are the solo
@@ -197,40 +197,20 @@ __global__ __launch_bounds__(256) void hermite6_ensemble_clock(const double* par
     if (threadIdx.x == 0) store_tally(t, block_status + blockIdx.x);
 }
 
-template <typename T, int S, bool STEP> hipError_t launch_s(const EnsembleHermite6Args<T>& a, unsigned long long grid, hipStream_t stream) {
-    (void)hipGetLastError();  // a launch reports ITS OWN error
-    hipLaunchKernelGGL((hermite6_ensemble_eval<T, S, STEP>), dim3(static_cast<unsigned>(grid)), dim3(64 * S), 0, stream, a);
-    return hipGetLastError();
-}
+static_assert(stream_lane_bodies<float>() == Lane<float>::W && stream_lane_bodies<double>() == Lane<double>::W, "plan_stream's bodies i per lane are the kernel's");
 
 template <typename T, bool STEP> hipError_t launch_planned(EnsembleHermite6Args<T> a, unsigned b, hipStream_t stream) {
-    const EnsembleHermite6Plan p = plan_hermite6_ensemble<T>(a.n, b);
-    a.groups_per_system          = p.groups;
-    switch (p.waves) {
-        case 1: return launch_s<T, 1, STEP>(a, p.grid_blocks, stream);
-        case 2: return launch_s<T, 2, STEP>(a, p.grid_blocks, stream);
-        case 4: return launch_s<T, 4, STEP>(a, p.grid_blocks, stream);
-        case 8: return launch_s<T, 8, STEP>(a, p.grid_blocks, stream);
-        default: return hipErrorInvalidValue;
-    }
+    const StreamPlan p  = plan_stream<T>(a.n, kHermite6Sums, hermite6_unroll_for<T>());
+    a.groups_per_system = p.groups;
+    return with_stream_waves(p.waves, [&](auto waves) {
+        constexpr int S = decltype(waves)::value;
+        (void)hipGetLastError();  // a launch reports ITS OWN error
+        hipLaunchKernelGGL((hermite6_ensemble_eval<T, S, STEP>), dim3(p.groups * b), dim3(64 * S), 0, stream, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
-
-// The geometry of one system is plan_hermite6's (hermite6_eval.hip), a function of (N, precision) alone; B only sets the grid.
-template <typename T> EnsembleHermite6Plan plan_hermite6_ensemble(unsigned n, unsigned b) {
-    constexpr int        W = Lane<T>::W;
-    const int            S = static_cast<int>(stream_waves(n));
-    EnsembleHermite6Plan p;
-    p.bodies_per_lane = W;
-    p.waves           = S;
-    p.unroll          = hermite6_unroll_for<T>();
-    p.groups          = (n + 64u * W - 1) / (64u * W);
-    p.block_threads   = 64u * S;
-    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 9 * W * 64 * sizeof(T));
-    p.grid_blocks     = static_cast<unsigned long long>(p.groups) * b;
-    return p;
-}
 
 template <typename T> hipError_t launch_ensemble6_pack(T* state12, const T* pos, const T* vel, const T* acc_in, T* zero, unsigned n, unsigned b, hipStream_t stream) {
     const unsigned partials = ensemble_partials(n);
@@ -265,8 +245,6 @@ hipError_t launch_ensemble6_clocks(const T* acc, const T* jerk, const T* snap, c
     return hipGetLastError();
 }
 
-template EnsembleHermite6Plan plan_hermite6_ensemble<float>(unsigned, unsigned);
-template EnsembleHermite6Plan plan_hermite6_ensemble<double>(unsigned, unsigned);
 template hipError_t launch_ensemble6_pack<float>(float*, const float*, const float*, const float*, float*, unsigned, unsigned, hipStream_t);
 template hipError_t launch_ensemble6_pack<double>(double*, const double*, const double*, const double*, double*, unsigned, unsigned, hipStream_t);
 template hipError_t launch_ensemble6_eval<float>(const EnsembleHermite6Args<float>&, unsigned, hipStream_t);

@@ -27,14 +27,6 @@ template <typename T> struct EnsembleHermite6Args {
     EnsembleSource<T> src;
 };
 
-struct EnsembleHermite6Plan {
-    int                bodies_per_lane, waves, unroll;
-    unsigned           groups;  // per system
-    unsigned           block_threads, lds_bytes;
-    unsigned long long grid_blocks;
-};
-
-template <typename T> EnsembleHermite6Plan plan_hermite6_ensemble(unsigned n, unsigned b);
 // state12 <- {pos, vel, acc_in} of every system (acc_in == nullptr: zeros); `zero` (may be nullptr): T[4 N B] set to 0 by the same launch
 template <typename T> hipError_t launch_ensemble6_pack(T* state12, const T* pos, const T* vel, const T* acc_in, T* zero, unsigned n, unsigned b, hipStream_t stream);
 template <typename T> hipError_t launch_ensemble6_eval(const EnsembleHermite6Args<T>& a, unsigned b, hipStream_t stream);
@@ -45,5 +37,18 @@ template <typename T> hipError_t launch_ensemble6_step(const EnsembleHermite6Arg
 template <typename T>
 hipError_t launch_ensemble6_clocks(const T* acc, const T* jerk, const T* snap, const T* crackle, unsigned n, unsigned b, T eta, T* dt_out, EnsembleClock* clocks, bool begin,
                                    const EnsembleSource<T>& src, double* partial, EnsembleStatus* block_status, EnsembleStatus* status, hipStream_t stream);
+
+// launch_hermite6_start (hermite6_kernels.h) for every system, through `state12` (T[12 N B]); softening^2 is the system's own.
+template <typename T>
+inline hipError_t launch_ensemble6_start(T* acc, T* jerk, T* snap, T* crackle, const T* pos, const T* vel, T* state12, unsigned n, unsigned b, T eps2, const T* system_eps2,
+                                         hipStream_t stream) {
+    EnsembleHermite6Args<T> a{};
+    a.state12 = state12, a.acc = acc, a.jerk = jerk, a.snap = snap, a.n = n, a.src.eps2 = eps2, a.src.system_eps2 = system_eps2;
+    // a and jerk do not depend on the accelerations: a first pass with b = 0, a second with that a for the snap
+    if (const auto err = launch_ensemble6_pack<T>(state12, pos, vel, nullptr, nullptr, n, b, stream); err != hipSuccess) return err;
+    if (const auto err = launch_ensemble6_eval<T>(a, b, stream); err != hipSuccess) return err;
+    if (const auto err = launch_ensemble6_pack<T>(state12, pos, vel, acc, crackle, n, b, stream); err != hipSuccess) return err;
+    return launch_ensemble6_eval<T>(a, b, stream);
+}
 
 }  // namespace nb

@@ -124,17 +124,7 @@ __global__ __launch_bounds__(256) void hermite6_predict(const T* pos, const T* v
     reinterpret_cast<vec4*>(state12)[3 * static_cast<size_t>(i) + 2] = ap;
 }
 
-__device__ __forceinline__ double block_min(double m, double* lds) {
-    const int tid = threadIdx.x;
-    lds[tid]      = m;
-    __syncthreads();
-#pragma unroll 1
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) lds[tid] = fmin(lds[tid], lds[tid + half]);
-        __syncthreads();
-    }
-    return lds[0];
-}
+#include "block_min.inc"
 
 template <typename T>
 __global__ __launch_bounds__(256) void hermite6_timestep_partial(const T* acc, const T* jerk, const T* snap, const T* crackle, unsigned n, double* partial) {
@@ -157,39 +147,19 @@ template <typename T> __global__ __launch_bounds__(256) void hermite6_timestep_f
     if (threadIdx.x == 0) dt_out[0] = static_cast<T>(static_cast<double>(eta) * __builtin_sqrt(m));
 }
 
-template <typename T, int S, bool STEP> hipError_t launch_s(const Hermite6Args<T>& a, const Hermite6Plan& p, hipStream_t stream) {
-    (void)hipGetLastError();  // a launch reports ITS OWN error
-    hipLaunchKernelGGL((hermite6_eval<T, S, STEP>), dim3(p.groups), dim3(64 * S), 0, stream, a);
-    return hipGetLastError();
-}
+static_assert(stream_lane_bodies<float>() == Lane<float>::W && stream_lane_bodies<double>() == Lane<double>::W, "plan_stream's bodies i per lane are the kernel's");
 
 template <typename T, bool STEP> hipError_t launch_planned(const Hermite6Args<T>& a, hipStream_t stream) {
-    const Hermite6Plan p = plan_hermite6<T>(a.n);
-    switch (p.waves) {
-        case 1: return launch_s<T, 1, STEP>(a, p, stream);
-        case 2: return launch_s<T, 2, STEP>(a, p, stream);
-        case 4: return launch_s<T, 4, STEP>(a, p, stream);
-        case 8: return launch_s<T, 8, STEP>(a, p, stream);
-        default: return hipErrorInvalidValue;
-    }
+    const StreamPlan p = plan_stream<T>(a.n, kHermite6Sums, hermite6_unroll_for<T>());
+    return with_stream_waves(p.waves, [&](auto waves) {
+        constexpr int S = decltype(waves)::value;
+        (void)hipGetLastError();  // a launch reports ITS OWN error
+        hipLaunchKernelGGL((hermite6_eval<T, S, STEP>), dim3(p.groups), dim3(64 * S), 0, stream, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
-
-// Geometry, a function of (N, precision) alone, as plan_hermite: one vector of bodies i per lane, S = stream_waves(N) waves that split j.
-// The fold's LDS holds 9 sums per body i and folded wave.
-template <typename T> Hermite6Plan plan_hermite6(unsigned n) {
-    constexpr int W = Lane<T>::W;
-    const int     S = static_cast<int>(stream_waves(n));
-    Hermite6Plan  p;
-    p.bodies_per_lane = W;
-    p.waves           = S;
-    p.unroll          = hermite6_unroll_for<T>();
-    p.groups          = (n + 64u * W - 1) / (64u * W);
-    p.block_threads   = 64u * S;
-    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 9 * W * 64 * sizeof(T));
-    return p;
-}
 
 template <typename T> hipError_t launch_hermite6_pack(T* workspace, const T* pos, const T* vel, const T* acc_in, T* zero, unsigned n, hipStream_t stream) {
     (void)hipGetLastError();
@@ -217,15 +187,13 @@ hipError_t launch_hermite6_timestep(const T* acc, const T* jerk, const T* snap, 
     return hipGetLastError();
 }
 
-template Hermite6Plan plan_hermite6<float>(unsigned);
-template Hermite6Plan plan_hermite6<double>(unsigned);
-template hipError_t   launch_hermite6_pack<float>(float*, const float*, const float*, const float*, float*, unsigned, hipStream_t);
-template hipError_t   launch_hermite6_pack<double>(double*, const double*, const double*, const double*, double*, unsigned, hipStream_t);
-template hipError_t   launch_hermite6_eval<float>(const Hermite6Args<float>&, hipStream_t);
-template hipError_t   launch_hermite6_eval<double>(const Hermite6Args<double>&, hipStream_t);
-template hipError_t   launch_hermite6_step<float>(const Hermite6Args<float>&, float*, hipStream_t);
-template hipError_t   launch_hermite6_step<double>(const Hermite6Args<double>&, double*, hipStream_t);
-template hipError_t   launch_hermite6_timestep<float>(const float*, const float*, const float*, const float*, unsigned, float, float*, double*, hipStream_t);
-template hipError_t   launch_hermite6_timestep<double>(const double*, const double*, const double*, const double*, unsigned, double, double*, double*, hipStream_t);
+template hipError_t launch_hermite6_pack<float>(float*, const float*, const float*, const float*, float*, unsigned, hipStream_t);
+template hipError_t launch_hermite6_pack<double>(double*, const double*, const double*, const double*, double*, unsigned, hipStream_t);
+template hipError_t launch_hermite6_eval<float>(const Hermite6Args<float>&, hipStream_t);
+template hipError_t launch_hermite6_eval<double>(const Hermite6Args<double>&, hipStream_t);
+template hipError_t launch_hermite6_step<float>(const Hermite6Args<float>&, float*, hipStream_t);
+template hipError_t launch_hermite6_step<double>(const Hermite6Args<double>&, double*, hipStream_t);
+template hipError_t launch_hermite6_timestep<float>(const float*, const float*, const float*, const float*, unsigned, float, float*, double*, hipStream_t);
+template hipError_t launch_hermite6_timestep<double>(const double*, const double*, const double*, const double*, unsigned, double, double*, double*, hipStream_t);
 
 }  // namespace nb

@@ -36,21 +36,24 @@ template <typename T> struct Hermite6Args {
     T        eps2;     // > 0 (the C boundary replaces 0 by the floor of nbody_hip_hermite6.h)
 };
 
-struct Hermite6Plan {
-    int      bodies_per_lane;  // I = W (one vector of bodies i per lane: fp32 a packed pair, fp64 one body)
-    int      waves;            // S
-    int      unroll;           // U bodies j per scalar load group
-    unsigned groups;           // workgroups
-    unsigned block_threads;
-    unsigned lds_bytes;
-};
+inline constexpr int kHermite6Sums = 9;  // ax ay az jx jy jz sx sy sz: the sums of plan_stream (wave_stream.h), with hermite6_unroll_for<T>()
 
-template <typename T> Hermite6Plan plan_hermite6(unsigned n);
 // workspace <- {pos, vel, acc_in} (acc_in == nullptr: zeros); `zero` (may be nullptr): T[4N] set to 0 by the same launch
 template <typename T> hipError_t launch_hermite6_pack(T* workspace, const T* pos, const T* vel, const T* acc_in, T* zero, unsigned n, hipStream_t stream);
 template <typename T> hipError_t launch_hermite6_eval(const Hermite6Args<T>& a, hipStream_t stream);
 template <typename T> hipError_t launch_hermite6_step(const Hermite6Args<T>& a, T* workspace, hipStream_t stream);
 template <typename T>
 hipError_t launch_hermite6_timestep(const T* acc, const T* jerk, const T* snap, const T* crackle, unsigned n, T eta, T* dt_out, double* scratch, hipStream_t stream);
+
+// The start of a 6th-order run, four launches: acc, jerk and snap of (pos, vel) and crackle = 0, through `state12` (T[12N]).
+template <typename T> inline hipError_t launch_hermite6_start(T* acc, T* jerk, T* snap, T* crackle, const T* pos, const T* vel, T* state12, unsigned n, T eps2, hipStream_t stream) {
+    Hermite6Args<T> a{};
+    a.state12 = state12, a.acc = acc, a.jerk = jerk, a.snap = snap, a.n = n, a.eps2 = eps2;
+    // a and jerk do not depend on the accelerations: a first pass with b = 0, a second with that a for the snap
+    if (const auto err = launch_hermite6_pack<T>(state12, pos, vel, nullptr, nullptr, n, stream); err != hipSuccess) return err;
+    if (const auto err = launch_hermite6_eval<T>(a, stream); err != hipSuccess) return err;
+    if (const auto err = launch_hermite6_pack<T>(state12, pos, vel, acc, crackle, n, stream); err != hipSuccess) return err;
+    return launch_hermite6_eval<T>(a, stream);
+}
 
 }  // namespace nb

@@ -2,7 +2,7 @@
 // of B independent systems of N bodies in one launch per stage, each system with a time step of its own.  gfx950 only; FMA contraction on.
 //
 // hermite_ensemble_eval<T, S, STEP> is hermite_eval (hermite_eval.hip) per system: workgroup g works on tile g mod G of system g / G, G the
-// workgroups plan_hermite gives one system of N bodies, S = stream_waves(N).  What lies between a lane's bodies i and its sums is the
+// workgroups plan_stream (wave_stream.h) gives one system of N bodies, S = stream_waves(N).  What lies between a lane's bodies i and its sums is the
 // same TEXT (hermite_stream.inc with wave_groups.inc, wave_mates.inc and wave_fold.inc inside it; hermite_body.h; hermite_correct.inc), so
 // a system's sums are formed in the order the solo kernel forms them and its bits are the solo call's.  Only the bases of the arrays, dt
 // and softening^2 are the system's own, all wave-uniform: a workgroup never touches two systems.
@@ -176,47 +176,27 @@ __global__ __launch_bounds__(256) void hermite_ensemble_clock(const double* part
     if (threadIdx.x == 0) store_tally(t, block_status + blockIdx.x);
 }
 
-template <typename T, int S, bool STEP> hipError_t launch_s(const EnsembleHermiteArgs<T>& a, unsigned long long grid, hipStream_t stream) {
-    (void)hipGetLastError();  // a launch reports ITS OWN error
-    hipLaunchKernelGGL((hermite_ensemble_eval<T, S, STEP>), dim3(static_cast<unsigned>(grid)), dim3(64 * S), 0, stream, a);
-    return hipGetLastError();
-}
+static_assert(stream_lane_bodies<float>() == Lane<float>::W && stream_lane_bodies<double>() == Lane<double>::W, "plan_stream's bodies i per lane are the kernel's");
 
 template <typename T, bool STEP> hipError_t launch_planned(EnsembleHermiteArgs<T> a, unsigned b, hipStream_t stream) {
-    const EnsembleHermitePlan p = plan_hermite_ensemble<T>(a.n, b);
-    a.groups_per_system         = p.groups;
-    switch (p.waves) {
-        case 1: return launch_s<T, 1, STEP>(a, p.grid_blocks, stream);
-        case 2: return launch_s<T, 2, STEP>(a, p.grid_blocks, stream);
-        case 4: return launch_s<T, 4, STEP>(a, p.grid_blocks, stream);
-        case 8: return launch_s<T, 8, STEP>(a, p.grid_blocks, stream);
-        default: return hipErrorInvalidValue;
-    }
+    const StreamPlan p  = plan_stream<T>(a.n, kHermiteSums, unroll_for<T>());
+    a.groups_per_system = p.groups;
+    return with_stream_waves(p.waves, [&](auto waves) {
+        constexpr int S = decltype(waves)::value;
+        (void)hipGetLastError();  // a launch reports ITS OWN error
+        hipLaunchKernelGGL((hermite_ensemble_eval<T, S, STEP>), dim3(p.groups * b), dim3(64 * S), 0, stream, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
 
-// The geometry of one system is plan_hermite's (hermite_eval.hip), a function of (N, precision) alone; B only sets the grid.
-template <typename T> EnsembleHermitePlan plan_hermite_ensemble(unsigned n, unsigned b) {
-    constexpr int       W = Lane<T>::W;
-    const int           S = static_cast<int>(stream_waves(n));
-    EnsembleHermitePlan p;
-    p.bodies_per_lane = W;
-    p.waves           = S;
-    p.unroll          = unroll_for<T>();
-    p.groups          = (n + 64u * W - 1) / (64u * W);
-    p.block_threads   = 64u * S;
-    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * W * 64 * sizeof(T));
-    p.grid_blocks     = static_cast<unsigned long long>(p.groups) * b;
-    return p;
-}
-
 template <typename T> hipError_t launch_ensemble_eval(const EnsembleHermiteArgs<T>& a, unsigned b, hipStream_t stream) { return launch_planned<T, false>(a, b, stream); }
 
 template <typename T> hipError_t launch_ensemble_step(const EnsembleHermiteArgs<T>& a, unsigned b, T* state8, hipStream_t stream) {
-    const EnsembleHermitePlan p = plan_hermite_ensemble<T>(a.n, b);
+    const StreamPlan p = plan_stream<T>(a.n, kHermiteSums, unroll_for<T>());
     (void)hipGetLastError();
-    hipLaunchKernelGGL((hermite_ensemble_predict<T>), dim3(static_cast<unsigned>(p.grid_blocks)), dim3(64), 0, stream, a.old_pos, static_cast<const T*>(a.vel),
+    hipLaunchKernelGGL((hermite_ensemble_predict<T>), dim3(p.groups * b), dim3(64), 0, stream, a.old_pos, static_cast<const T*>(a.vel),
                        static_cast<const T*>(a.acc), static_cast<const T*>(a.jerk), state8, a.n, p.groups, a.src);
     if (const auto err = hipGetLastError(); err != hipSuccess) return err;
     return launch_planned<T, true>(a, b, stream);
@@ -237,12 +217,10 @@ hipError_t launch_ensemble_clocks(const T* acc, const T* jerk, unsigned n, unsig
     return hipGetLastError();
 }
 
-template EnsembleHermitePlan plan_hermite_ensemble<float>(unsigned, unsigned);
-template EnsembleHermitePlan plan_hermite_ensemble<double>(unsigned, unsigned);
-template hipError_t          launch_ensemble_eval<float>(const EnsembleHermiteArgs<float>&, unsigned, hipStream_t);
-template hipError_t          launch_ensemble_eval<double>(const EnsembleHermiteArgs<double>&, unsigned, hipStream_t);
-template hipError_t          launch_ensemble_step<float>(const EnsembleHermiteArgs<float>&, unsigned, float*, hipStream_t);
-template hipError_t          launch_ensemble_step<double>(const EnsembleHermiteArgs<double>&, unsigned, double*, hipStream_t);
+template hipError_t launch_ensemble_eval<float>(const EnsembleHermiteArgs<float>&, unsigned, hipStream_t);
+template hipError_t launch_ensemble_eval<double>(const EnsembleHermiteArgs<double>&, unsigned, hipStream_t);
+template hipError_t launch_ensemble_step<float>(const EnsembleHermiteArgs<float>&, unsigned, float*, hipStream_t);
+template hipError_t launch_ensemble_step<double>(const EnsembleHermiteArgs<double>&, unsigned, double*, hipStream_t);
 template hipError_t launch_ensemble_clocks<float>(const float*, const float*, unsigned, unsigned, float, float*, EnsembleClock*, bool, const EnsembleSource<float>&, double*,
                                                   EnsembleStatus*, EnsembleStatus*, hipStream_t);
 template hipError_t launch_ensemble_clocks<double>(const double*, const double*, unsigned, unsigned, double, double*, EnsembleClock*, bool, const EnsembleSource<double>&,

@@ -49,17 +49,7 @@ template <typename T, bool STEP> __device__ __forceinline__ bool system_paramete
     return true;
 }
 
-__device__ __forceinline__ double block_min(double m, double* lds) {
-    const int tid = threadIdx.x;
-    lds[tid]      = m;
-    __syncthreads();
-#pragma unroll 1
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) lds[tid] = fmin(lds[tid], lds[tid + half]);
-        __syncthreads();
-    }
-    return lds[0];
-}
+#include "block_min.inc"
 
 // what one system, or a block of them, adds to the status record
 struct Tally {

@@ -6,7 +6,7 @@
 
 #include <cstdint>
 
-#include "wave_stream.h"
+#include "hermite_kernels.h"  // kHermiteSums
 
 namespace nb {
 
@@ -56,20 +56,13 @@ template <typename T> struct EnsembleHermiteArgs {
     EnsembleSource<T> src;
 };
 
-struct EnsembleHermitePlan {
-    int                bodies_per_lane, waves, unroll;
-    unsigned           groups;  // per system
-    unsigned           block_threads, lds_bytes;
-    unsigned long long grid_blocks;
-};
-
 // doubles of partial minima per system, and the layout of the workspace behind the predicted state
 inline unsigned ensemble_partials(unsigned n) { return (n + kEnsembleTimestepBodies - 1) / kEnsembleTimestepBodies; }
 inline unsigned ensemble_status_blocks(unsigned b) { return (b + kEnsembleClockSystems - 1) / kEnsembleClockSystems; }
 
-template <typename T> EnsembleHermitePlan plan_hermite_ensemble(unsigned n, unsigned b);
-template <typename T> hipError_t          launch_ensemble_eval(const EnsembleHermiteArgs<T>& a, unsigned b, hipStream_t stream);
-template <typename T> hipError_t          launch_ensemble_step(const EnsembleHermiteArgs<T>& a, unsigned b, T* state8, hipStream_t stream);
+// The geometry of one system is the solo call's, plan_stream (wave_stream.h) of (N, precision) alone; B only sets the grid, groups * B.
+template <typename T> hipError_t launch_ensemble_eval(const EnsembleHermiteArgs<T>& a, unsigned b, hipStream_t stream);
+template <typename T> hipError_t launch_ensemble_step(const EnsembleHermiteArgs<T>& a, unsigned b, T* state8, hipStream_t stream);
 // partial minima of every system -> partial[b * ensemble_partials(n)]; then per system: dt_out[s] = eta (T)min (dt_out != nullptr),
 // or the clock of the system begun (begin) / advanced by the rule of the header (src.clocks != nullptr), with one partial status record per
 // kEnsembleClockSystems systems; then (status != nullptr) the records summed into status.

@@ -117,17 +117,7 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_predict(con
 
 #include "hermite_ratio.h"
 
-__device__ __forceinline__ double block_min(double m, double* lds) {
-    const int tid = threadIdx.x;
-    lds[tid]      = m;
-    __syncthreads();
-#pragma unroll 1
-    for (int half = 128; half > 0; half >>= 1) {
-        if (tid < half) lds[tid] = fmin(lds[tid], lds[tid + half]);
-        __syncthreads();
-    }
-    return lds[0];
-}
+#include "block_min.inc"
 
 template <typename T> __global__ __launch_bounds__(256) void hermite_timestep_partial(const T* acc, const T* jerk, unsigned n, double* partial) {
     using vec4 = typename Lane<T>::vec4;
@@ -148,41 +138,19 @@ template <typename T> __global__ __launch_bounds__(256) void hermite_timestep_fi
     if (threadIdx.x == 0) dt_out[0] = eta * static_cast<T>(m);  // m: the smallest |a| / |jerk| (hermite_ratio.h)
 }
 
-template <typename T, int S, bool STEP> hipError_t launch_s(const HermiteArgs<T>& a, const HermitePlan& p, hipStream_t stream) {
-    (void)hipGetLastError();  // a launch reports ITS OWN error
-    hipLaunchKernelGGL((hermite_eval<T, S, STEP>), dim3(p.groups), dim3(64 * S), 0, stream, a);
-    return hipGetLastError();
-}
+static_assert(stream_lane_bodies<float>() == Lane<float>::W && stream_lane_bodies<double>() == Lane<double>::W, "plan_stream's bodies i per lane are the kernel's");
 
 template <typename T, bool STEP> hipError_t launch_planned(const HermiteArgs<T>& a, hipStream_t stream) {
-    const HermitePlan p = plan_hermite<T>(a.n);
-    switch (p.waves) {
-        case 1: return launch_s<T, 1, STEP>(a, p, stream);
-        case 2: return launch_s<T, 2, STEP>(a, p, stream);
-        case 4: return launch_s<T, 4, STEP>(a, p, stream);
-        case 8: return launch_s<T, 8, STEP>(a, p, stream);
-        default: return hipErrorInvalidValue;
-    }
+    const StreamPlan p = plan_stream<T>(a.n, kHermiteSums, unroll_for<T>());
+    return with_stream_waves(p.waves, [&](auto waves) {
+        constexpr int S = decltype(waves)::value;
+        (void)hipGetLastError();  // a launch reports ITS OWN error
+        hipLaunchKernelGGL((hermite_eval<T, S, STEP>), dim3(p.groups), dim3(64 * S), 0, stream, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
-
-// Geometry, a function of (N, precision) alone.  One vector of bodies i per lane (I = W: 12 state vectors, 6 second-level sums and two
-// chains of 9 temporaries compile to 103 - 118 VGPRs; a second vector does not fit under 128), so a workgroup owns 64 W bodies i.  S, the waves that split j
-// (stream_waves, wave_stream.h), is the largest power of two up to 8 that still gives every wave a whole chunk of 128 bodies j: from
-// 65 536 bodies (fp32; 32 768 fp64) the grid alone puts 16 waves on every CU of the MI355X.
-template <typename T> HermitePlan plan_hermite(unsigned n) {
-    constexpr int W = Lane<T>::W;
-    const int     S = static_cast<int>(stream_waves(n));
-    HermitePlan   p;
-    p.bodies_per_lane = W;
-    p.waves           = S;
-    p.unroll          = unroll_for<T>();
-    p.groups          = (n + 64u * W - 1) / (64u * W);
-    p.block_threads   = 64u * S;
-    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * 6 * W * 64 * sizeof(T));
-    return p;
-}
 
 template <typename T> hipError_t launch_hermite_eval(const HermiteArgs<T>& a, hipStream_t stream) { return launch_planned<T, false>(a, stream); }
 
@@ -203,13 +171,11 @@ template <typename T> hipError_t launch_hermite_timestep(const T* acc, const T* 
     return hipGetLastError();
 }
 
-template HermitePlan plan_hermite<float>(unsigned);
-template HermitePlan plan_hermite<double>(unsigned);
-template hipError_t  launch_hermite_eval<float>(const HermiteArgs<float>&, hipStream_t);
-template hipError_t  launch_hermite_eval<double>(const HermiteArgs<double>&, hipStream_t);
-template hipError_t  launch_hermite_step<float>(const HermiteArgs<float>&, float*, hipStream_t);
-template hipError_t  launch_hermite_step<double>(const HermiteArgs<double>&, double*, hipStream_t);
-template hipError_t  launch_hermite_timestep<float>(const float*, const float*, unsigned, float, float*, double*, hipStream_t);
-template hipError_t  launch_hermite_timestep<double>(const double*, const double*, unsigned, double, double*, double*, hipStream_t);
+template hipError_t launch_hermite_eval<float>(const HermiteArgs<float>&, hipStream_t);
+template hipError_t launch_hermite_eval<double>(const HermiteArgs<double>&, hipStream_t);
+template hipError_t launch_hermite_step<float>(const HermiteArgs<float>&, float*, hipStream_t);
+template hipError_t launch_hermite_step<double>(const HermiteArgs<double>&, double*, hipStream_t);
+template hipError_t launch_hermite_timestep<float>(const float*, const float*, unsigned, float, float*, double*, hipStream_t);
+template hipError_t launch_hermite_timestep<double>(const double*, const double*, unsigned, double, double*, double*, hipStream_t);
 
 }  // namespace nb

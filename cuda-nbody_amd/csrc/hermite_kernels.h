@@ -32,18 +32,10 @@ template <typename T> struct HermiteArgs {
     T        eps2;     // > 0 (the C boundary replaces 0 by the floor of nbody_hip_hermite.h)
 };
 
-struct HermitePlan {
-    int      bodies_per_lane;  // I = W (one vector of bodies i per lane: fp32 a packed pair, fp64 one body)
-    int      waves;            // S
-    int      unroll;           // U bodies j per scalar load group
-    unsigned groups;           // workgroups
-    unsigned block_threads;
-    unsigned lds_bytes;
-};
+inline constexpr int kHermiteSums = 6;  // ax ay az jx jy jz: the sums of plan_stream (wave_stream.h), with unroll_for<T>()
 
-template <typename T> HermitePlan plan_hermite(unsigned n);
-template <typename T> hipError_t  launch_hermite_eval(const HermiteArgs<T>& a, hipStream_t stream);
-template <typename T> hipError_t  launch_hermite_step(const HermiteArgs<T>& a, T* workspace, hipStream_t stream);
-template <typename T> hipError_t  launch_hermite_timestep(const T* acc, const T* jerk, unsigned n, T eta, T* dt_out, double* scratch, hipStream_t stream);
+template <typename T> hipError_t launch_hermite_eval(const HermiteArgs<T>& a, hipStream_t stream);
+template <typename T> hipError_t launch_hermite_step(const HermiteArgs<T>& a, T* workspace, hipStream_t stream);
+template <typename T> hipError_t launch_hermite_timestep(const T* acc, const T* jerk, unsigned n, T eta, T* dt_out, double* scratch, hipStream_t stream);
 
 }  // namespace nb

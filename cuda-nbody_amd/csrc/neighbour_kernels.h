@@ -33,7 +33,7 @@ struct NeighbourTile {  // what a survey workgroup leaves of its tile for the st
 };
 
 // ---- geometry: a function of (N, precision) alone -----------------------------------------------------------------------------------
-__host__ __device__ inline unsigned neighbour_waves(unsigned n) {  // S, as plan_hermite
+__host__ __device__ inline unsigned neighbour_waves(unsigned n) {  // S, as plan_stream
     unsigned s = 1;
     while (s < 8 && 2 * s * kNeighbourChunk <= n) s *= 2;
     return s;

@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace nb {
 
 inline constexpr unsigned kChunk      = 128;  // bodies j per wave and chunk
@@ -44,6 +46,56 @@ __host__ __device__ inline StreamGeom stream_geometry(unsigned n, unsigned count
     g.ranges            = 1;
     while (g.ranges < need && g.ranges < cap) g.ranges *= 2;
     return g;
+}
+
+// Bodies i per lane, one vector of them: fp32 a packed pair, fp64 one body (Lane<T>::W of nbody_lane.h, which lives inside the units' own
+// namespaces; the evaluation units hold the two against each other).
+template <typename T> constexpr int stream_lane_bodies() { return sizeof(T) == 8 ? 1 : 2; }
+
+// The geometry of an evaluation of every body i of a system against every body j (hermite_eval, hermite6_eval and their ensembles), a
+// function of (N, precision) alone.  One vector of bodies i per lane (I = W: 12 state vectors, 6 second-level sums and two chains of 9
+// temporaries compile to 103 - 118 VGPRs; a second vector does not fit under 128), so a workgroup owns 64 W bodies i.  S = stream_waves(N):
+// from 65 536 bodies (fp32; 32 768 fp64) the grid alone puts 16 waves on every CU of the MI355X.  The fold's LDS holds `sums` sums (6; 9
+// with the snap) per body i and folded wave.  An ensemble launches `groups` workgroups per system.
+struct StreamPlan {
+    int      bodies_per_lane;  // I = W
+    int      waves;            // S
+    int      unroll;           // U bodies j per scalar load group
+    unsigned groups;           // workgroups
+    unsigned block_threads;
+    unsigned lds_bytes;
+};
+template <typename T> inline StreamPlan plan_stream(unsigned n, int sums, int unroll) {
+    constexpr int W = stream_lane_bodies<T>();
+    const int     S = static_cast<int>(stream_waves(n));
+    StreamPlan    p;
+    p.bodies_per_lane = W;
+    p.waves           = S;
+    p.unroll          = unroll;
+    p.groups          = (n + 64u * W - 1) / (64u * W);
+    p.block_threads   = 64u * S;
+    p.lds_bytes       = static_cast<unsigned>((S > 1 ? S - 1 : 1) * sums * W * 64 * sizeof(T));
+    return p;
+}
+// ... into the fields that nb_hermite_plan_t, nb_hermite6_plan_t and nb_hermite_ensemble_plan_t share
+template <typename Out> void fill(Out* out, const StreamPlan& p) {
+    out->bodies_per_lane = p.bodies_per_lane;
+    out->waves_per_group = p.waves;
+    out->unroll          = p.unroll;
+    out->groups          = p.groups;
+    out->block_threads   = p.block_threads;
+    out->lds_bytes       = p.lds_bytes;
+}
+
+// The launch of a kernel compiled for S = 1, 2, 4 and 8 waves: `launch` is called with S as a std::integral_constant.
+template <typename Launch> hipError_t with_stream_waves(unsigned waves, Launch&& launch) {
+    switch (waves) {
+        case 1: return launch(std::integral_constant<int, 1>{});
+        case 2: return launch(std::integral_constant<int, 2>{});
+        case 4: return launch(std::integral_constant<int, 4>{});
+        case 8: return launch(std::integral_constant<int, 8>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace nb

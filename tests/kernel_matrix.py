@@ -164,7 +164,7 @@ def _pair_cases():
 
 
 # The libraries dispatched by N alone: S, the waves that split j, is 1 below 256 bodies, 2 from 256, 4 from 512, 8 from 1 024
-# (plan_ensemble_fast, plan_hermite, block_waves, neighbour_waves).  The sizes sit on and around every switch point -- a wave gets exactly
+# (plan_ensemble_fast, plan_stream, block_waves, neighbour_waves).  The sizes sit on and around every switch point -- a wave gets exactly
 # one chunk, then one chunk and one ragged body -- and inside the S = 4 window.
 N_BY_WAVES = {1: (255,), 2: (256, 257, 511), 4: (512, 513, 700, 1023), 8: (1024, 1025)}
 MASSES = ("equal", "species", "random")

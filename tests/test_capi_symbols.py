@@ -175,11 +175,20 @@ def test_capi_check_under_address_and_ub_sanitizers(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert run.returncode == 0 and "capi check ok" in run.stdout and run.stderr == "", (run.stdout[-2000:], run.stderr[-3000:])
     csrc = os.path.join(ROOT, "cuda-nbody_amd", "csrc")
-    boundaries = sorted(f for f in os.listdir(csrc) if f.endswith("_capi.hip"))
-    assert len(boundaries) == 10
+    read = lambda name: open(os.path.join(csrc, name)).read()  # noqa: E731
+    boundaries = sorted(f for f in os.listdir(csrc) if f.endswith(("_capi.hip", "_boundary.hip")))
+    assert len(boundaries) == 13
     for name in boundaries:
-        text = open(os.path.join(csrc, name)).read()
-        assert '#include "capi_check.h"' in text and "struct Span" not in text and not re.search(r"\bbool spans_ok\(", text), name
+        # a boundary's text: the file and the host-only shape headers (*_boundary.h) it is written in, those they include too
+        names, k = [name], 0
+        while k < len(names):
+            names += [h for h in re.findall(r'^#include "(\w+_boundary\.h)"', read(names[k]), re.M) if h not in names]
+            k += 1
+        assert '#include "capi_check.h"' in "".join(read(part) for part in names), names
+        assert re.search(r"\b(spans_ok|in_place_or_apart)\(\{", "".join(read(part) for part in names)), names  # ... and it is used
+    for name in os.listdir(csrc):
+        if name.endswith((".hip", ".h", ".inc", ".cpp")) and name != "capi_check.h":
+            assert "struct Span" not in read(name) and not re.search(r"\bbool spans_ok\(", read(name)), name
 
 
 def test_strict_translation_unit_has_no_fused_multiply_add():

@@ -203,7 +203,7 @@ def test_hermite_streaming_loops_keep_their_mix():
 
 
 def test_hermite_sources_keep_the_scalar_unit_to_loads():
-    for name in ("hermite_eval.hip", "hermite_capi.hip", "hermite_kernels.h"):
+    for name in ("hermite_eval.hip", "hermite_capi.hip", "hermite_boundary.h", "hermite_kernels.h"):
         src = open(os.path.join(CSRC, name)).read().lower()
         for word in ("s_" + "store", "s_buffer_" + "store", "s_scratch_" + "store", "s_" + "atomic", "s_buffer_" + "atomic", "s_dcache_" + "wb", "s_dcache_" + "discard", "atomicadd"):
             assert word not in src, (name, word)

@@ -32,7 +32,7 @@ CSRC = os.path.join(ROOT, "cuda-nbody_amd", "csrc")
 HEADER = "nbody_hip_hermite6_ensemble.h"
 NAMES = ("plan", "eval", "init", "step", "timestep", "begin", "advance")
 SYMBOLS = sorted(["nb_hermite6_ensemble_workspace_bytes"] + [f"nb_hermite6_ensemble_{name}_{sfx}" for name in NAMES for sfx in ("f32", "f64")])
-NEW_SOURCES = ("hermite6_ensemble.hip", "hermite6_ensemble_kernels.h", "hermite6_ensemble_boundary.hip")
+NEW_SOURCES = ("hermite6_ensemble.hip", "hermite6_ensemble_kernels.h", "hermite6_ensemble_boundary.hip", "hermite_ensemble_boundary.h")
 # --eta of --integrator=hermite6-ensemble where none is given: DESIGN.md 5.16's table (a numpy fp64 restatement of both schemes)
 DEFAULT_ETA = 0.025
 STATE = ("pos", "vel", "acc", "jerk", "snap", "crackle")
@@ -322,7 +322,7 @@ def test_hermite6_ensemble_sources_use_no_atomics_and_share_the_text():
         text = open(os.path.join(CSRC, name)).read()
         for word in ("atomic", "hipMalloc", "hipFree", "Synchronize", "mutex", "static "):
             assert word not in text, (name, word)
-    boundary = open(os.path.join(CSRC, "hermite6_ensemble_boundary.hip")).read()
+    boundary = open(os.path.join(CSRC, "hermite6_ensemble_boundary.hip")).read() + open(os.path.join(CSRC, "hermite_ensemble_boundary.h")).read()  # the file and the shape header it is written in
     assert '#include "capi_check.h"' in boundary and '#include "softening_floor.h"' in boundary and "static_assert(" in boundary
     assert not os.path.exists(os.path.join(CSRC, "hermite6_ensemble_capi.hip"))
 

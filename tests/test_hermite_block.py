@@ -224,7 +224,7 @@ def test_block_streaming_loops_keep_their_mix():
 
 
 def test_block_sources_keep_the_scalar_unit_to_loads():
-    for name in ("hermite_block.hip", "hermite_block_capi.hip", "hermite_block_kernels.h", "hermite_stream.h", "hermite_stream.inc"):
+    for name in ("hermite_block.hip", "hermite_block_capi.hip", "hermite_block_boundary.h", "hermite_block_kernels.h", "hermite_stream.h", "hermite_stream.inc"):
         src = open(os.path.join(CSRC, name)).read().lower()
         for word in ("s_" + "store", "s_buffer_" + "store", "s_scratch_" + "store", "s_" + "atomic", "s_buffer_" + "atomic", "s_dcache_" + "wb", "s_dcache_" + "discard", "atomicadd",
                      "atomic_", "hipmalloc", "synchronize", "printf", "mutex"):
