@@ -53,6 +53,9 @@ HERMITE6_BLOCK_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_BLOCK_LIB", os.path
 HERMITE6_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite6_ensemble.so"))
 # 6th-order block time steps of many systems in one launch per stage (include/nbody_hip_hermite6_block_ensemble.h): a library of its own
 HERMITE6_BLOCK_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_HERMITE6_BLOCK_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_hermite6_block_ensemble.so"))
+# The energies of every system of an ensemble in one call, and the drift between two measurements (include/nbody_hip_energy_ensemble.h): a
+# library of its own, loaded by energy_ensemble_lib().
+ENERGY_ENSEMBLE_LIB_PATH = os.environ.get("NBODY_HIP_ENERGY_ENSEMBLE_LIB", os.path.join(HERE, "libnbody_hip_energy_ensemble.so"))
 
 NB_MODE_STRICT, NB_MODE_FAST = 0, 1
 NB_SHARD_ACC_IN, NB_SHARD_FINALIZE = 1, 2
@@ -554,6 +557,30 @@ HERMITE6_BLOCK_ENSEMBLE_SIGNATURES = {
     "nb_hermite6_block_ensemble_summary": (_ci, [_vp, _cu, _vp, _vp]),
 }
 
+# include/nbody_hip_energy_ensemble.h: exported by libnbody_hip_energy_ensemble.so, and nothing else is
+class EnergyEnsemblePlan(ctypes.Structure):
+    """nb_energy_ensemble_plan_t: the geometry of a measurement, a function of (N, precision) but for the grid"""
+    _fields_ = [("bodies_per_lane", _ci), ("waves_per_group", _ci), ("groups_per_system", _cu), ("block_threads", _cu), ("lds_bytes", _cu), ("reserved", _cu),
+                ("grid_blocks", ctypes.c_ulonglong)]
+
+
+class EnergyDrift(ctypes.Structure):
+    """nb_energy_ensemble_drift_t: 64 bytes of device memory nb_energy_ensemble_drift writes"""
+    _fields_ = [("worst_relative_drift", _cd), ("rms_relative_drift", _cd), ("worst_momentum_drift", _cd), ("systems", _cu), ("worst_system", _cu),
+                ("worst_momentum_system", _cu), ("not_finite", _cu), ("reserved", ctypes.c_ulonglong * 3)]
+
+
+ENERGY_ENSEMBLE_SIGNATURES = {
+    "nb_energy_ensemble_plan_f32": (_ci, [_cu, _cu, _P(EnergyEnsemblePlan)]),
+    "nb_energy_ensemble_plan_f64": (_ci, [_cu, _cu, _P(EnergyEnsemblePlan)]),
+    "nb_energy_ensemble_workspace_bytes": (_ci, [_cu, _cu, _P(_sz)]),
+    # positions velocities N B | softening_sq system_softening_sq softening_stride | workspace workspace_bytes | device_results stream
+    "nb_energy_ensemble_f32": (_ci, [_vp, _vp, _cu, _cu, _cf, _vp, _cu, _vp, _sz, _vp, _vp]),
+    "nb_energy_ensemble_f64": (_ci, [_vp, _vp, _cu, _cu, _cd, _vp, _cu, _vp, _sz, _vp, _vp]),
+    # start end B | device_summary stream
+    "nb_energy_ensemble_drift": (_ci, [_vp, _vp, _cu, _vp, _vp]),
+}
+
 _lib = None
 _loaded = {}  # path -> the library at that path, its signatures set
 _lab = os.environ.get("NBODY_HIP_LAB") == "1"
@@ -652,6 +679,11 @@ def field_lib() -> ctypes.CDLL:
 def knn_lib() -> ctypes.CDLL:
     """Load libnbody_hip_knn.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
     return _load(KNN_LIB_PATH, KNN_SIGNATURES)
+
+
+def energy_ensemble_lib() -> ctypes.CDLL:
+    """Load libnbody_hip_energy_ensemble.so (fails loudly when it has not been built).  Its errors are named by lib().nb_error_string."""
+    return _load(ENERGY_ENSEMBLE_LIB_PATH, ENERGY_ENSEMBLE_SIGNATURES)
 
 
 def check(code: int, what: str = "nbody_hip") -> None:
@@ -2066,8 +2098,69 @@ def energy(positions, velocities, num_bodies: int, dtype=np.float32, workspace=N
         result.free()
         if own:
             workspace.free()
+    return energy_dict(out)
+
+
+def energy_dict(out: Energy) -> dict:
     return {"kinetic": out.kinetic, "potential": out.potential, "total": out.total, "mass": out.mass, "momentum": tuple(out.momentum),
             "angular_momentum": tuple(out.angular_momentum), "center_of_mass": tuple(out.center_of_mass)}
+
+
+def energy_ensemble_plan(num_bodies: int, num_systems: int, dtype=np.float32) -> EnergyEnsemblePlan:
+    """nb_energy_ensemble_plan_*: the geometry of a measurement of `num_systems` systems of `num_bodies` bodies"""
+    return _plan(energy_ensemble_lib, "energy_ensemble", EnergyEnsemblePlan, dtype, num_bodies, num_systems)
+
+
+def energy_ensemble_workspace_bytes(num_bodies: int, num_systems: int) -> int:
+    """nb_energy_ensemble_workspace_bytes: scratch memory nb_energy_ensemble_* needs (either precision)"""
+    need = _sz(0)
+    check(energy_ensemble_lib().nb_energy_ensemble_workspace_bytes(num_bodies, num_systems, ctypes.byref(need)), "nb_energy_ensemble_workspace_bytes")
+    return need.value
+
+
+def energy_ensemble(positions, velocities, num_bodies: int, num_systems: int, dtype=np.float32, softening_sq=0.0, system_softening_sq=None,
+                    softening_stride: int = 1, workspace=None, results=None, stream=None) -> list:
+    """nb_energy_ensemble_* of the device arrays `positions` / `velocities` (raw device addresses, 4 * num_bodies * num_systems elements):
+    one dict per system with the keys of energy().  `softening_sq`: the scalar; `system_softening_sq`: a device address, system s reads
+    element s * softening_stride of it.  `workspace`: a DeviceBuffer of at least energy_ensemble_workspace_bytes(...) bytes; `results`: a
+    DeviceBuffer of 104 * num_systems bytes that keeps the records on the device (for energy_ensemble_drift); None = allocated for the
+    call.  Blocks until the results are back on the host."""
+    own_workspace, own_results = workspace is None, results is None
+    if own_workspace:
+        workspace = DeviceBuffer(energy_ensemble_workspace_bytes(num_bodies, num_systems))
+    if own_results:
+        results = DeviceBuffer(ctypes.sizeof(Energy) * num_systems)
+    check(lib().nb_stream_synchronize(None), "nb_stream_synchronize")  # (DeviceBuffer clears on the null stream; `stream` may not wait for it)
+    try:
+        f32 = np.dtype(dtype) == np.float32
+        fn = energy_ensemble_lib().nb_energy_ensemble_f32 if f32 else energy_ensemble_lib().nb_energy_ensemble_f64
+        check(fn(positions, velocities, num_bodies, num_systems, np.float32(softening_sq) if f32 else float(softening_sq), system_softening_sq, softening_stride,
+                 workspace.ptr, workspace.nbytes, results.ptr, stream), "nb_energy_ensemble")
+        out = (Energy * num_systems)()
+        check(lib().nb_d2h(ctypes.byref(out), results.ptr, ctypes.sizeof(out), stream), "nb_d2h(energy_ensemble)")
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+    finally:
+        if own_results:
+            results.free()
+        if own_workspace:
+            workspace.free()
+    return [energy_dict(e) for e in out]
+
+
+def energy_ensemble_drift(start, end, num_systems: int, stream=None) -> dict:
+    """nb_energy_ensemble_drift of two device arrays of `num_systems` nb_energy_t (DeviceBuffers or raw addresses): the 64-byte record as a
+    dict.  Blocks until it is back on the host."""
+    summary = DeviceBuffer(ctypes.sizeof(EnergyDrift))
+    check(lib().nb_stream_synchronize(None), "nb_stream_synchronize")
+    try:
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        check(energy_ensemble_lib().nb_energy_ensemble_drift(ptr(start), ptr(end), num_systems, summary.ptr, stream), "nb_energy_ensemble_drift")
+        out = EnergyDrift()
+        check(lib().nb_d2h(ctypes.byref(out), summary.ptr, ctypes.sizeof(out), stream), "nb_d2h(energy_ensemble_drift)")
+        check(lib().nb_stream_synchronize(stream), "nb_stream_synchronize")
+    finally:
+        summary.free()
+    return {name: getattr(out, name) for name, _ in EnergyDrift._fields_ if name != "reserved"}
 
 
 def comm_transport_info(comm) -> dict:

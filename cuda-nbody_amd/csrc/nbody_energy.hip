@@ -37,8 +37,6 @@ constexpr int      kWaves   = 4;            // waves per workgroup
 constexpr int      kThreads = 64 * kWaves;
 constexpr unsigned kChunk   = 128;          // bodies j per unit: the longest fp32 sum
 constexpr int      kR       = 4;            // vectors of bodies i per lane (I = kR * W)
-constexpr int      kFields  = 12;           // potential sum, 2*kinetic, mass, momentum[3], angular momentum[3], sum m p[3]
-constexpr unsigned kRecord  = 16;           // doubles per workgroup record (12 used)
 constexpr unsigned kTargetWorkgroups = 2048;
 
 template <typename T> constexpr unsigned block_bodies() { return 64u * kR * Lane<T>::W; }
@@ -51,59 +49,7 @@ template <typename T> struct EnergyArgs {
     T        eps2;
 };
 
-// The fixed tree over the kThreads threads of a workgroup: field f of thread 0 ends up holding the sum.  Same shape every launch.
-__device__ __forceinline__ void tree_sum(double (&lds)[kFields][kThreads], const double (&v)[kFields]) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int f = 0; f < kFields; ++f) lds[f][t] = v[f];
-    __syncthreads();
-#pragma unroll 1
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int f = 0; f < kFields; ++f) lds[f][t] += lds[f][t + s];
-        }
-        __syncthreads();
-    }
-}
-
-// m_j / sqrt(d2) (fp32: one v_rsq_f32 per body, 1 ulp; fp64: seed + series)
-template <typename T> __device__ __forceinline__ typename Lane<T>::vec inv_sqrt(typename Lane<T>::vec d2);
-template <> __device__ __forceinline__ v2f inv_sqrt<float>(v2f d2) { return v2f{__builtin_amdgcn_rsqf(d2.x), __builtin_amdgcn_rsqf(d2.y)}; }
-template <> __device__ __forceinline__ double inv_sqrt<double>(double d2) {
-    const double y0 = __builtin_amdgcn_rsq(d2);
-    const double r  = __builtin_fma(-d2, y0 * y0, 1.0);
-    return __builtin_fma(y0 * r, __builtin_fma(r, 0.375, 0.5), y0);
-}
-
-// The bodies j of [j0, j1) against the lane's bodies i: acc[r] += m_j / |p_i - p_j|_eps.  DIAG: only j > i counts.
-template <typename T, bool DIAG, typename Stream>
-__device__ __forceinline__ void sweep(Stream bodies, unsigned j0, unsigned j1, const typename Lane<T>::vec (&px)[kR], const typename Lane<T>::vec (&py)[kR], const typename Lane<T>::vec (&pz)[kR],
-                                      const unsigned (&idx)[kR * Lane<T>::W], typename Lane<T>::vec eps2, typename Lane<T>::vec (&acc)[kR]) {
-    using LT      = Lane<T>;
-    using vec     = typename LT::vec;
-    constexpr int W = LT::W;
-#pragma unroll 4
-    for (unsigned j = j0; j < j1; ++j) {
-        const typename LT::raw4 b = bodies[j];
-        const vec bx = LT::splat(b.x), by = LT::splat(b.y), bz = LT::splat(b.z), bm = LT::splat(b.w);
-#pragma unroll
-        for (int r = 0; r < kR; ++r) {
-            const vec dx = bx - px[r];
-            const vec dy = by - py[r];
-            const vec dz = bz - pz[r];
-            vec       d2 = LT::fma(dx, dx, eps2);
-            d2           = LT::fma(dy, dy, d2);
-            d2           = LT::fma(dz, dz, d2);
-            vec inv      = inv_sqrt<T>(d2);
-            if constexpr (DIAG) {
-#pragma unroll
-                for (int w = 0; w < W; ++w) LT::set(inv, w, j > idx[r * W + w] ? LT::get(inv, w) : T(0));
-            }
-            acc[r] = LT::fma(bm, inv, acc[r]);
-        }
-    }
-}
+#include "energy_pair.inc"  // kFields, kRecord, tree_sum, inv_sqrt, sweep: shared with energy_ensemble.hip
 
 template <typename T> __global__ __launch_bounds__(kThreads) void energy_pairs(EnergyArgs<T> e) {
     using LT              = Lane<T>;
@@ -157,8 +103,8 @@ template <typename T> __global__ __launch_bounds__(kThreads) void energy_pairs(E
         vec acc[kR];
 #pragma unroll
         for (int r = 0; r < kR; ++r) acc[r] = LT::splat(0);
-        if (d == 0) sweep<T, true>(bodies, j0, j1, px, py, pz, idx, eps2, acc);
-        else        sweep<T, false>(bodies, j0, j1, px, py, pz, idx, eps2, acc);
+        if (d == 0) sweep<T, true, kR>(bodies, j0, j1, px, py, pz, idx, eps2, acc);
+        else        sweep<T, false, kR>(bodies, j0, j1, px, py, pz, idx, eps2, acc);
 #pragma unroll
         for (int k = 0; k < I; ++k) {
             if (idx[k] < e.n) pot = __builtin_fma(static_cast<double>(mi[k]), static_cast<double>(LT::get(acc[k / W], k % W)), pot);

@@ -37,6 +37,9 @@ template <std::floating_point T> class BodyEnsembleHIP {
     }
     auto get_positions(std::span<T> out) const -> void { pos_[read_].download(out); }
     auto get_velocities(std::span<T> out) const -> void { vel_.download(out); }
+    // the current state on the device (T[4*N*B] each, for a diagnostic that reads it in place)
+    auto positions_device() const noexcept -> const T* { return pos_[read_].data(); }
+    auto velocities_device() const noexcept -> const T* { return vel_.data(); }
 
     // One step of every system: new positions into the other array, then the two swap.  `device_params`: null (every system uses
     // dt, damping, softening_sq) or a device array T[4*B] of {dt, damping, softening^2, -} per system.

@@ -56,6 +56,9 @@ template <std::floating_point T, int Order> class BodyEnsembleHIPHermiteOrder {
     }
     auto get_positions(std::span<T> out) const -> void { pos_.download(out); }
     auto get_velocities(std::span<T> out) const -> void { vel_.download(out); }
+    // the current state on the device (T[4*N*B] each, for a diagnostic that reads it in place)
+    auto positions_device() const noexcept -> const T* { return pos_.data(); }
+    auto velocities_device() const noexcept -> const T* { return vel_.data(); }
 
     // one step of every system with the same dt
     auto update(T dt, nb_stream_t stream = nullptr) -> void {

@@ -105,6 +105,9 @@ template <std::floating_point T, int Order> class BodyEnsembleHIPHermiteBlockOrd
     }
     auto get_positions(std::span<T> out) const -> void { pos_out_.download(out); }
     auto get_velocities(std::span<T> out) const -> void { vel_out_.download(out); }
+    // the snapshot of the last sync() on the device (T[4*N*B] each, for a diagnostic that reads it in place)
+    auto positions_device() const noexcept -> const T* { return pos_out_.data(); }
+    auto velocities_device() const noexcept -> const T* { return vel_out_.data(); }
 
  private:
     auto n() const noexcept { return static_cast<unsigned>(num_bodies_); }

@@ -1,17 +1,57 @@
-// ensemble_cli.cpp -- `nbody --systems=<B>` (ensemble_cli.hpp)
+// ensemble_cli.cpp -- `nbody --systems=<B>` (ensemble_cli.hpp), and its --energies
 #include "ensemble_cli.hpp"
 
 #include "bodyensemblehip.hpp"
 #include "bodyensemblehip_hermite.hpp"
 #include "bodyensemblehip_hermite_block.hpp"
 #include "cli_common.hpp"
+#include "ensemble_energy_hip.hpp"
 #include "text.hpp"
 
 #include <algorithm>
 #include <cstdio>
+#include <optional>
+#include <string>
 #include <vector>
 
 namespace {
+
+// --energies: every system's energy measured on the device where the run keeps its state (EnsembleEnergyHIP), at the start and at the end;
+// two lines after the run's own output.  Without the flag nothing is allocated and nothing is launched.
+template <typename T> class EnergyReport {
+ public:
+    EnergyReport(const EnsembleRun& run, T softening_sq) : softening_sq_(softening_sq) {
+        if (run.energies) meter_.emplace(run.num_bodies, run.num_systems);
+    }
+    template <typename Ensemble> auto start(const Ensemble& ensemble) -> void {
+        if (!meter_) return;
+        meter_->measure(ensemble.positions_device(), ensemble.velocities_device(), softening_sq_);
+        start_ = meter_->results();
+    }
+    // `how_far`: "<K> steps" or "t = <T>"
+    template <typename Ensemble> auto end(const Ensemble& ensemble, const std::string& how_far) -> void {
+        if (!meter_) return;
+        meter_->measure(ensemble.positions_device(), ensemble.velocities_device(), softening_sq_);
+        const auto drift = meter_->drift_since(start_);
+        auto totals = std::vector<double>();
+        for (const auto& e : start_) totals.push_back(e.total);
+        std::sort(totals.begin(), totals.end());
+        std::printf("energies start: systems=%zu total_min=%.9g total_median=%.9g total_max=%.9g\n", start_.size(), totals.front(), totals[totals.size() / 2], totals.back());
+        std::printf("energies end (%s): worst_system=%u relative_drift_max=%.9g relative_drift_rms=%.9g momentum_drift_max=%.9g not_finite=%u\n", how_far.c_str(), drift.worst_system,
+                    drift.worst_relative_drift, drift.rms_relative_drift, drift.worst_momentum_drift, drift.not_finite);
+    }
+    static auto steps(std::size_t k) -> std::string { return std::to_string(k) + " steps"; }
+    static auto time(double t) -> std::string {
+        char text[48];
+        std::snprintf(text, sizeof text, "t = %g", t);
+        return text;
+    }
+
+ private:
+    T                                   softening_sq_;
+    std::optional<EnsembleEnergyHIP<T>> meter_;
+    std::vector<nb_energy_t>            start_;
+};
 
 // --integrator=hermite-ensemble: --steps=K takes K fixed steps of --integrator=hermite's dt; --t-end runs the adaptive form, batches of calls
 // between reads of the 64-byte status record; --benchmark times `iterations` fixed steps after one untimed, B N^2 interactions per step.
@@ -24,6 +64,8 @@ template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRu
     const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
     auto ensemble = Ensemble(n, b, softening_sq);
     ensemble.set_state(pos, vel);
+    auto energies = EnergyReport<T>(run, softening_sq);
+    energies.start(ensemble);
     if (run.benchmark) {
         ensemble.update(dt);  // (untimed, as Compute::run_benchmark)
         HipEvent start, stop;
@@ -40,6 +82,7 @@ template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRu
         std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
         std::printf("= %s %s-precision GFLOP/s at %d flops per %s interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(),
                     sizeof(T) == 8 ? "double" : "single", flops, run.sixth ? "acceleration + jerk + snap" : "acceleration + jerk");
+        energies.end(ensemble, energies.steps(1 + static_cast<std::size_t>(run.iterations)));
         return;
     }
     if (run.t_end > 0.0) {
@@ -64,6 +107,7 @@ template <typename T, typename Ensemble> auto run_hermite_typed(const EnsembleRu
         ensemble.get_velocities(vel);
         write_dump<T>(run.dump, pos, vel);
     }
+    energies.end(ensemble, run.t_end > 0.0 ? energies.time(run.t_end) : energies.steps(run.steps));
 }
 
 // --integrator=hermite-block-ensemble: dt_max = dt; --t-end=T (or --steps=K: T = K dt) runs every system to the last block step not past
@@ -78,6 +122,11 @@ template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun&
     const auto   params = nb_hermite_block_params_t{run.eta, 0.01, dt_max, run.levels, 0};
     auto         ensemble = Ensemble(n, b, softening_sq, params);
     ensemble.set_state(pos, vel);
+    auto energies = EnergyReport<T>(run, softening_sq);
+    if (run.energies) {
+        ensemble.sync();  // (the snapshot at time 0: the state as uploaded)
+        energies.start(ensemble);
+    }
     const auto report = [&](const char* what, const nb_hermite_block_ensemble_summary_t& from, const nb_hermite_block_ensemble_summary_t& to) {
         const auto   body_steps  = to.body_steps - from.body_steps;
         const double evaluations = static_cast<double>(body_steps) / static_cast<double>(n);
@@ -98,6 +147,10 @@ template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun&
         std::printf("= %s ms per interval\n", text::width3(milliseconds / static_cast<float>(run.iterations)).c_str());
         report("= ", warm, end);
         std::printf("= %s billion interactions per second\n", text::width3(static_cast<float>(interactions * 1e-9 / (static_cast<double>(milliseconds) * 1e-3))).c_str());
+        if (run.energies) {
+            ensemble.sync();
+            energies.end(ensemble, energies.time(static_cast<double>(1 + run.iterations) * dt_max));
+        }
         return;
     }
     const auto   none  = ensemble.summary();
@@ -115,6 +168,10 @@ template <typename T, typename Ensemble> auto run_block_typed(const EnsembleRun&
     std::printf("%zu bodies x %zu systems, %s integrator, eta %g, %d levels, to t = %g: %u systems stopped\n", n, b, name, run.eta, run.levels, t_end, end.stopped);
     std::printf("block steps per system: fewest %llu, median %llu, most %llu\n", steps.front(), steps[steps.size() / 2], steps.back());
     report("", none, end);
+    if (run.energies) {
+        ensemble.sync();  // every system at its own last time not past t_end
+        energies.end(ensemble, energies.time(t_end));
+    }
 }
 
 // --systems without a Hermite integrator: BodyEnsembleHIP's leapfrog steps
@@ -126,6 +183,8 @@ template <typename T> auto run_plain_typed(const EnsembleRun& run, std::vector<T
     // BodySystemHIP's conversions: dt and damping float -> T, softening^2 = T(s) * T(s)
     const T dt = static_cast<T>(run.params.time_step), damping = static_cast<T>(run.params.damping);
     const T softening = static_cast<T>(run.params.softening), softening_sq = softening * softening;
+    auto energies = EnergyReport<T>(run, softening_sq);
+    energies.start(ensemble);
     if (run.benchmark) {
         ensemble.update(dt, damping, softening_sq);  // (untimed, as Compute::run_benchmark)
         HipEvent start, stop;
@@ -140,6 +199,7 @@ template <typename T> auto run_plain_typed(const EnsembleRun& run, std::vector<T
         std::printf("%zu bodies x %zu systems, total time for %d iterations: %s ms\n", n, b, run.iterations, text::width3(milliseconds).c_str());
         std::printf("= %s billion interactions per second\n", text::width3(interactions).c_str());
         std::printf("= %s %s-precision GFLOP/s at %d flops per interaction\n", text::width3(interactions * static_cast<float>(flops)).c_str(), sizeof(T) == 8 ? "double" : "single", flops);
+        energies.end(ensemble, energies.steps(1 + static_cast<std::size_t>(run.iterations)));
         return;
     }
     for (std::size_t s = 0; s < run.steps; ++s) ensemble.update(dt, damping, softening_sq);
@@ -148,6 +208,7 @@ template <typename T> auto run_plain_typed(const EnsembleRun& run, std::vector<T
         ensemble.get_velocities(vel);
         write_dump<T>(run.dump, pos, vel);
     }
+    energies.end(ensemble, energies.steps(run.steps));
 }
 
 }  // namespace

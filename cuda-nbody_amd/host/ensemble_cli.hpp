@@ -26,6 +26,7 @@ struct EnsembleRun {
     double                eta = 0.02;       // hermite, adaptive: the accuracy parameter of the systems' time steps (--eta); block: of the bodies'
     bool                  block = false;    // --integrator=hermite-block-ensemble or hermite6-block-ensemble: dt_max = params.time_step; --t-end, or --steps=K intervals of dt_max
     int                   levels = 30;      // block: the deepest level (--levels)
+    bool                  energies = false; // --energies: every system's energy at the start and at the end (EnsembleEnergyHIP), two lines
 };
 
 // Starts from the current rand() state (main has applied --seed): system 0 is the single-system start-up state (the same three

@@ -8,6 +8,7 @@
 //                     --mode=fast|strict  --config=shell|random|expand  --demo=<0..6>  --steps=<n>  --dump=<file>
 //                     --seed=<n>  --graph  --no-workspace  --workspace-mib=<n>  --energy  --neighbours=<radius>  --knn=<K>  --field=<file>  --inject-error=<x> (test hook for --compare)  --alloc-limit-mib=<n> (test hook)
 //                     --systems=<B> (B independent systems of --numbodies bodies in one launch: libnbody_hip_ensemble.so)
+//                     --energies (with --systems: every system's energy at the start and the end in one call each: libnbody_hip_energy_ensemble.so)
 //                     --integrator=hermite (4th-order Hermite steps: libnbody_hip_hermite.so)
 //                     --integrator=hermite6 (6th-order Hermite steps: libnbody_hip_hermite6.so)
 //                     --integrator=hermite-block (... with block time steps: libnbody_hip_hermite_block.so)
@@ -78,6 +79,7 @@ struct Options {
     bool                  graph = false;
     bool                  no_workspace = false;
     bool                  energy = false;  // print the energy at the start and the end of a --benchmark / --steps run
+    bool                  energies = false;  // --systems: print what the run did to the energy of every system (the start, the drift at the end)
     std::optional<double> neighbours;  // --neighbours=<radius>: after the run, the closest pair, the neighbour counts within the radius, the deepest potential
     std::optional<unsigned> knn;  // --knn=<K>: after the run, the density centre, the density and core radii, the densest body, the Lagrangian radii
     std::vector<double>   field_points;  // --field=<file>: x y z of the points where the final state's acceleration and potential are printed
@@ -132,6 +134,11 @@ Options:
                               one region of reaction planes; default: what the library asks for, at most a third of the device's memory)
   --energy                    With --benchmark or --steps: print the kinetic, potential and total energy and the momentum before and
                               after the run, and the relative drift of the total energy (one device only)
+  --energies                  With --systems (required; every --integrator=*-ensemble too) and --benchmark, --steps or --t-end: measure the
+                              energy of every system at the start and at the end, in one call each (outside --benchmark's timed
+                              region; the block ensembles are synchronised first), and print the smallest, median and largest total
+                              energy at the start and, at the end, the system whose total drifted most, the largest and the rms
+                              relative drift, the largest momentum drift and the systems whose drift is not finite
   --neighbours FLOAT          After a --benchmark, --steps or --dump run: print the closest pair of bodies and its separation, the mean and
                               the largest number of neighbours within this radius (>= 0) and its body, the deepest potential and its
                               body (one device only, at most 16777216 bodies; accepted wherever --energy is)
@@ -238,6 +245,7 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
         else if (name == "graph") ok = flag(options.graph);
         else if (name == "no-workspace" || name == "no_workspace") ok = flag(options.no_workspace);
         else if (name == "energy") ok = flag(options.energy);
+        else if (name == "energies") ok = flag(options.energies);
         else if (name == "numbodies") {
             const auto v = take_value();
             ok           = v && parse_number(*v, options.numbodies) && options.numbodies >= 1;
@@ -392,6 +400,8 @@ auto parse_args(int argc, char** argv) -> std::pair<Status, Options> {
     if (options.energy && options.devices.size() > 1) return error("--energy is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
     if (options.energy && (options.compare || options.qatest)) return error("--energy cannot be combined with --compare or --qatest (those runs step two systems)");
 
+    if (options.energies && options.systems == 0) return error("--energies measures every system of a --systems run: it needs --systems (one system: --energy)");
+
     if (options.neighbours && options.devices.size() > 1) return error("--neighbours is single-device: it cannot be combined with --numdevices or --devices naming more than one GPU");
     if (options.neighbours && (options.compare || options.qatest)) return error("--neighbours cannot be combined with --compare or --qatest (those runs step two systems)");
     if (options.neighbours && options.numbodies > NB_NEIGHBOUR_MAX_BODIES) return error("--neighbours: --numbodies must be at most 16777216");
@@ -516,6 +526,7 @@ auto main(int argc, char** argv) -> int {
             run.eta         = cmd_options.eta.value_or(cmd_options.hermite6_ensemble ? kHermite6EnsembleEta : cmd_options.hermite6_block_ensemble ? 0.2 : run.eta);
             run.block       = cmd_options.hermite_block_ensemble;
             run.levels      = cmd_options.levels.value_or(run.levels);
+            run.energies    = cmd_options.energies;
             run_ensemble(run);
             return 0;
         }
