@@ -292,7 +292,23 @@ NB_API int nb_graph_destroy(nb_graph_t graph);
  *  The potential is the Plummer potential whose negative gradient is exactly the force the integrate kernels apply, so with
  *  damping = 1 its drift measures only integrator and rounding error.  It EXCLUDES the i = j term.  An energy that sums over all
  *  ordered pairs i, j including i = j (as the numpy energy() of tests/test_gpu_parity.py does) differs from `total` by the constant
- *  -1/2 sum_i m_i^2 / eps (eps > 0). */
+ *  -1/2 sum_i m_i^2 / eps (eps > 0).
+ *
+ *  Operand range.  One pair's term m_i m_j / sqrt(d^2 + eps^2) is held (tests/test_fast_domain.py, tests/test_energy_domain.py) to
+ *  1e-6 (fp32) / 1e-14 (fp64) of its magnitude for d^2 + eps^2 in [2^-83, 2^84] (fp32) / [2^-599, 2^601] (fp64), the range the tests
+ *  cover; outside it nothing is clamped.  Every unordered pair and every body's O(N) terms are counted exactly once: a system in
+ *  which only two bodies, or one, have a mass gives the bits of those bodies alone.  fp32 sums run over at most
+ *  128 (nb_energy_f32) / 64 (nb_energy_ensemble_f32) bodies j before they are multiplied by m_i and folded into fp64; the O(N) terms
+ *  are fp64 throughout.
+ *  Non-finite inputs are ordinary data and stay where the definitions put them.  A NaN coordinate makes the potential, the total,
+ *  that component of the centre of mass and the other two components of the angular momentum NaN, and nothing else.  An infinite mass
+ *  makes the kinetic energy, the mass and every component of the momentum and the angular momentum infinite, and the potential (its
+ *  own masked i = j term is m * 0), the total and the centre of mass NaN.  A NaN velocity component reaches the kinetic energy, the
+ *  total, that component of the momentum and the other two of the angular momentum; the potential, the mass and the centre of mass
+ *  keep their bits.  Zero-mass bodies contribute nothing when eps^2 > 0 or when they coincide with no body; a zero-mass body ON
+ *  another body with eps^2 == 0 is 0 * inf = NaN in the potential and the total, so pad with bodies that lie apart, or soften.
+ *  With nb_energy_ensemble_* (nbody_hip_energy_ensemble.h) all of this holds system by system: no other system of the batch changes a
+ *  bit. */
 typedef struct nb_energy {
     double kinetic;              /* 1/2 sum_i m_i |v_i|^2                                                         */
     double potential;            /* - sum_{i<j} m_i m_j / sqrt(|p_i - p_j|^2 + eps^2)   (i = j excluded)          */

@@ -13,13 +13,29 @@
  * Layout: the ensembles' own.  B systems of N bodies each; system s holds bodies [s*N, (s+1)*N) of
  *   positions  T[4*N*B] = {x, y, z, mass} per body
  *   velocities T[4*N*B] = {vx, vy, vz, w} per body (.w is ignored)
- * Both are only read, and nothing past element 4*N*B of either is read.  Zero-mass padding bodies contribute nothing.
+ * Both are only read, and nothing past element 4*N*B of either is read.  Zero-mass padding bodies contribute nothing when eps^2 > 0 or
+ * when they coincide with no body (below: Operand range).
  *
  * What one call computes.  device_results[s] is exactly the nb_energy_t (104 bytes) nb_energy_* gives for system s alone, with the
  * same definitions: the Plummer potential -sum_{i<j} m_i m_j / sqrt(|p_i - p_j|^2 + eps^2) over the pairs of that system, the i = j
  * term masked (not subtracted), G = 1.  NO SOFTENING FLOOR: eps^2 is used as given.  The Hermite kernels replace a softening^2 of 0
  * by a floor of their own; this potential does not, so with eps^2 == 0 two bodies at one place give an infinite potential here.
- * fp32 sums never run over more than 128 bodies j before they are multiplied by m_i and folded into fp64; the O(N) terms are fp64.
+ * fp32 sums never run over more than 64 bodies j before they are multiplied by m_i and folded into fp64; the O(N) terms are fp64.
+ *
+ * Operand range.  That of nb_energy_* (nbody_hip.h, "Operand range"), system by system.  One pair's term m_i m_j / sqrt(d^2 + eps^2)
+ * is held (tests/test_fast_domain.py, tests/test_energy_domain.py) to 1e-6 (fp32) / 1e-14 (fp64) of its magnitude for
+ * d^2 + eps^2 in [2^-83, 2^84] (fp32) / [2^-599, 2^601] (fp64), the range the tests cover; outside it nothing is clamped.  In every
+ * geometry of nb_energy_ensemble_plan_* every unordered pair and every body's O(N) terms are counted exactly once: a system in
+ * which only two bodies, or one, have a mass gives the bits of those bodies alone.  fp32 sums run over at most
+ * 128 (nb_energy_f32) / 64 (nb_energy_ensemble_f32) bodies j.
+ * Non-finite inputs are ordinary data, and no other system of the batch changes a bit.  A NaN coordinate makes its system's
+ * potential, total, that component of the centre of mass and the other two components of the angular momentum NaN, and nothing
+ * else.  An infinite mass makes the kinetic energy, the mass and every component of the momentum and the angular momentum infinite,
+ * and the potential (its own masked i = j term is m * 0), the total and the centre of mass NaN.  A NaN velocity component reaches the
+ * kinetic energy, the total, that component of the momentum and the other two of the angular momentum; the potential, the mass and
+ * the centre of mass keep their bits.  Zero-mass bodies contribute nothing when eps^2 > 0 or when they coincide with no body; a
+ * zero-mass body ON another body with eps^2 == 0 is 0 * inf = NaN in the potential and the total, so pad with bodies that lie apart,
+ * or soften.
  *
  * Softening.  system_softening_sq == NULL: every system uses softening_sq.  Otherwise system s reads
  * system_softening_sq[s * softening_stride] (device memory, softening_stride >= 1) and the scalar is ignored.  Stride 1 is the

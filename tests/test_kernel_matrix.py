@@ -1,18 +1,21 @@
 """Every compiled kernel instantiation against a long double sum (the registry: tests/kernel_matrix.py).
 
-CPU part: the nine listings of `make asm` hold exactly the kernels the registry names -- a new `case` in a dispatch switch, or a case taken
+CPU part: the ten registered listings of `make asm` (the nine of the step, Hermite and neighbour kernels, and energy_ensemble.s; the Makefile's
+other nine are named as out of scope) hold exactly the kernels the registry names -- a new `case` in a dispatch switch, or a case taken
 out of the registry, fails here with the kernel's name -- and every case's shape makes the plan query select the instantiation it claims
 (the one-sided and pairwise queries with the CU count a machine without a device reports; the GPU part reads them again on the device).
 
 GPU part: one parametrised test per shape-dispatched family, one parameter per case: set the override, assert that the plan query selects
 the claimed instantiation, run it through the public entry point, restore the override, and compare with long double sums -- the
 project's own references and bounds, imported from the modules that define them (test_gpu_parity.direct_sum_f64, test_fast_domain's TOL,
-UNIT_ROUNDOFF and check_step, the checkers of test_hermite, test_hermite_block and test_neighbour).
+UNIT_ROUNDOFF and check_step, the checkers of test_hermite, test_hermite_block and test_neighbour; for energy_ensemble_pairs the probe
+pairs and probe bodies of test_energy_domain, which count every pair and every body once, bit for bit).
 
 How a one-sided case sizes its ranges (nb_integrate_shard_*, i and j independent) is in stream_launches / wavesplit_launches below: each
 instantiation meets a ragged i range that does not start at 0, a j range that starts off a multiple of 4, a ragged last chunk with an odd
 number of groups, fewer chunks than waves, in fp32 enough chunks per wave for the second-level sums, chunks of all three mass forms and a
 first body j of mass zero."""
+import ctypes
 import hashlib
 import os
 import subprocess
@@ -24,6 +27,7 @@ import kernel_matrix as km
 from conftest import ROOT
 from test_ensemble import T as as_T
 from test_ensemble import eps2_of, step as ensemble_step, systems as ensemble_systems
+from test_energy_domain import ensemble_probe_bodies, ensemble_probe_pairs
 from test_fast_domain import TOL, UNIT_ROUNDOFF, check_step
 from test_gpu_parity import direct_sum_f64, gpu_accel, run_gpu
 from test_hermite import check_eval, check_one_step, cloud, evaluate
@@ -66,6 +70,9 @@ def test_symbol_parser_reads_template_arguments():
 
 def test_the_listings_and_the_registry_name_the_same_kernels():
     """both directions, by name: a compiled kernel the registry does not know; a kernel the registry names that is not compiled"""
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        built = next(line for line in f if line.startswith("ASM :=")).split()[2:]
+    assert len(km.LISTINGS) == 10 and len(km.UNREGISTERED) == 9 and sorted(km.LISTINGS + km.UNREGISTERED) == sorted(built), "a listing neither registered nor named as out of scope"
     compiled = [k for kernels in listed().values() for k in kernels]
     assert len(compiled) == len(set(compiled)), "a kernel is compiled into two listings"
     registry = km.registry()
@@ -82,7 +89,7 @@ def test_the_listings_and_the_registry_name_the_same_kernels():
             assert registry[kernel] == "other", km.kernel_name(kernel)
     sizes = {family: sum(1 for k in compiled if k[0] == family) for family in km.FAMILIES}
     assert sizes == {"integrate_bodies_fast": 45, "integrate_bodies_wavesplit": 20, "pair_forces": 32, "ensemble_fast": 8, "hermite_eval": 16,
-                     "hermite_block_eval": 8, "neighbour_survey": 16}, sizes
+                     "hermite_block_eval": 8, "neighbour_survey": 16, "energy_ensemble_pairs": 12}, sizes
 
 
 def test_every_other_kernel_names_an_existing_test():
@@ -109,6 +116,8 @@ def query(pkg, case, n=None, i_count=None, j_count=None):
         return pkg.hermite_plan(n, case.dtype)
     if case.family == "hermite_block_eval":
         return pkg.hermite_block_plan(n, n, case.dtype)
+    if case.family == "energy_ensemble_pairs":
+        return pkg.energy_ensemble_plan(n, 1, case.dtype)
     return pkg.neighbour_plan(n, case.dtype)
 
 
@@ -151,6 +160,24 @@ def test_n_dispatched_cases_select_their_instantiation_on_the_host(pkg):
             got = (pkg.ensemble_plan(n, 1, dtype).waves_per_group, pkg.hermite_plan(n, dtype).waves_per_group, pkg.hermite_block_plan(n, 1, dtype).waves_per_group,
                    pkg.neighbour_plan(n, dtype).waves_per_group)
             assert got == (want,) * 4, (n, got)
+    # the energies of an ensemble: every case at the first or the last n of its window, every window with both, and every n from 1 to
+    # 65 536 inside the window of the instantiation its plan selects -- so of the twelve compiled kernels only the ten with a case are ever
+    # asked for (the other two: UNREACHABLE, test_unreachable_reasons_hold)
+    for dtype in (F32, F64):
+        cases = [c for c in km.cases_of("energy_ensemble_pairs") if c.dtype == dtype]
+        for case in cases:
+            assert plan_fields(query(pkg, case, n=dict(case.shape)["n"]), case) == case.plan, case.id
+        assert sorted((c.args, dict(c.shape)["n"]) for c in cases) == sorted({(shape, n) for shape, first, last in km.ENERGY_ENSEMBLE_WINDOWS[dtype] for n in (first, last)})
+        w = km.LANE_WIDTH[dtype]
+        for shape, first, last in km.ENERGY_ENSEMBLE_WINDOWS[dtype]:
+            for n in range(first, last + 1):
+                p = pkg.energy_ensemble_plan(n, 1, dtype)
+                assert (p.bodies_per_lane // w, p.waves_per_group) == shape, (km.TYPE_NAME[dtype], n, shape)
+        windows = km.ENERGY_ENSEMBLE_WINDOWS[dtype]
+        assert windows[0][1] == 1 and windows[-1][2] == 65536 and all(a[2] + 1 == b[1] for a, b in zip(windows, windows[1:]))
+        idle = {u.kernel[1][1:] for u in km.UNREACHABLE if u.kind == "energy_plan" and u.kernel[1][0] == km.TYPE_NAME[dtype]}
+        compiled = {k[1][1:] for k in listed()["energy_ensemble.s"] if k[0] == "energy_ensemble_pairs" and k[1][0] == km.TYPE_NAME[dtype]}
+        assert {shape for shape, _, _ in windows} == {c.args for c in cases} == compiled - idle and idle <= compiled
 
 
 def test_overridden_cases_select_their_instantiation_on_the_host(pkg):
@@ -170,14 +197,24 @@ def test_overridden_cases_select_their_instantiation_on_the_host(pkg):
 
 def test_unreachable_reasons_hold(pkg):
     """pair_forces<T, 8, 16>: asked for through the override, every size needs more LDS than a CU has; no default plan has 16 waves.
-    integrate_bodies_fast<T, R, 16, 4>: the override refuses the tile, and no plan with 16 waves -- default or forced -- has it."""
+    integrate_bodies_fast<T, R, 16, 4>: the override refuses the tile, and no plan with 16 waves -- default or forced -- has it.
+    energy_ensemble_pairs<float, 2, 1> and <float, 4, 2>: the plan query, which nothing overrides, selects them for no n in [1, 65 536]."""
     assert {u.kernel for u in km.UNREACHABLE} == ({("pair_forces", (t, 8, 16)) for t in ("float", "double")} |
-                                                  {("integrate_bodies_fast", (t, r, 16, 4)) for t, rs in (("float", (1, 2)), ("double", (1, 2, 4))) for r in rs})
+                                                  {("integrate_bodies_fast", (t, r, 16, 4)) for t, rs in (("float", (1, 2)), ("double", (1, 2, 4))) for r in rs} |
+                                                  {("energy_ensemble_pairs", ("float", 2, 1)), ("energy_ensemble_pairs", ("float", 4, 2))})
     shapes = [(i, j) for i in (1, 63, 300, 1000, 4096, 8193, 20000, 32768, 40001, 65536, 131072, 262144, 1048576) for j in (i, 37, 2048, 5000, 1048576)]
     for u in km.UNREACHABLE:
         dtype = km.DTYPE_OF[u.kernel[1][0]]
         name = km.kernel_name(u.kernel)
-        if u.kind == "pair_lds":
+        if u.kind == "energy_plan":
+            assert not u.override and dtype == F32
+            r, s = u.kernel[1][1:]
+            for n in range(1, 65537):
+                p = pkg.energy_ensemble_plan(n, 1, dtype)
+                assert (p.bodies_per_lane // km.LANE_WIDTH[dtype], p.waves_per_group) != (r, s), f"{name}: n = {n} selects it now -- give the kernel a case"
+            plan = pkg.EnergyEnsemblePlan()  # past the last n the query answers nothing
+            assert pkg.energy_ensemble_lib().nb_energy_ensemble_plan_f32(65537, 1, ctypes.byref(plan)) == 10001
+        elif u.kind == "pair_lds":
             with forced(pkg, u.override):
                 for n in km.PAIR_SIZES:
                     p = pkg.pair_plan(n, dtype)
@@ -526,3 +563,14 @@ def test_neighbour_survey(gpu, case):
         check_cloud(gpu, dtype, n, km.MASSES, (0.01, 0.0))
     else:
         check_cloud(gpu, dtype, n, ("equal",), ())
+
+
+@gpu_only
+@pytest.mark.parametrize("case", km.cases_of("energy_ensemble_pairs"), ids=ids(km.cases_of("energy_ensemble_pairs")))
+def test_energy_ensemble_pairs(gpu, case):
+    """the probe pairs and the probe bodies of test_energy_domain at the first and the last size of the instantiation's window: every pair
+    among the geometry's edge indices (every pair at all up to 130 bodies) and each of those bodies' O(N) terms counted once, bit for bit"""
+    n, dtype = dict(case.shape)["n"], case.dtype
+    assert plan_fields(gpu.energy_ensemble_plan(n, 1, dtype), case) == case.plan, f"{case.id}: the plan query selects {plan_fields(gpu.energy_ensemble_plan(n, 1, dtype), case)}"
+    ensemble_probe_pairs(gpu, dtype, n, case.id)
+    ensemble_probe_bodies(gpu, dtype, n, case.id)

@@ -53,7 +53,7 @@ def main(trace_dir, out_path):
     others = [k for k in listed if k[0] not in km.FAMILIES]
     lines = ["kernel matrix: the kernels of a rocprofv3 --kernel-trace run of `pytest tests/test_kernel_matrix.py -m gpu` against the listings of `make asm`",
              f"trace files read: {len(files)}; dispatches of this project's kernels: {sum(seen.values())}; distinct kernels traced: {len(seen)}",
-             f"kernels in the nine listings: {len(listed)}; of shape-dispatched families: {len(dispatched)}; of these reachable: {len(reachable)}, UNREACHABLE: {len(dispatched) - len(reachable)}",
+             f"kernels in the {len(km.LISTINGS)} registered listings: {len(listed)}; of shape-dispatched families: {len(dispatched)}; of these reachable: {len(reachable)}, UNREACHABLE: {len(dispatched) - len(reachable)}",
              f"compiled, reachable, shape-dispatched kernels missing from the trace: {len(missing)}"]
     lines += [f"    MISSING {km.kernel_name(k)}" for k in missing]
     lines += ["", "traced kernels that no listing holds: " + str(len([k for k in seen if k not in set(listed)]))]
