@@ -1,7 +1,13 @@
-"""The kernel matrix: every __global__ function the ten registered listings of `make -C cuda-nbody_amd/csrc asm` hold (LISTINGS), and what
-checks it.  The Makefile builds nineteen listings: the other nine (field.s, knn.s, nbody_pair_lead.s, hermite_ensemble.s,
-hermite_block_ensemble.s, hermite6_eval.s, hermite6_block.s, hermite6_ensemble.s, hermite6_block_ensemble.s) are in no registry yet and
-are out of this module's scope: UNREGISTERED names them, and the test module asserts that the two lists are all the Makefile builds.
+"""The kernel matrix: every __global__ function the fifteen registered listings of `make -C cuda-nbody_amd/csrc asm` hold (LISTINGS), and
+what checks it.  The Makefile builds nineteen listings: the other four (field.s, knn.s, hermite_ensemble.s, hermite6_ensemble.s) have a
+registry of their own, on the same terms, in the test module of their library: REGISTERED_ELSEWHERE names the listing, the module and the
+registry function (as strings: those modules import this one), and the test module asserts that each exists and that the two tables are
+all the Makefile builds.
+
+A kernel is (listing, (function name, template arguments)): the block-step units share kernel text by include (hermite_block_schedule.inc,
+hermite_block_ensemble_schedule.inc), so block_scan and its like are compiled into two listings under one symbol -- two code objects, two
+libraries, each with a test of its own.  SHARED_TEXT names those kernels and their listings; the test module asserts that no listing holds
+a symbol twice and that SHARED_TEXT is exactly what is compiled more than once.
 
 Three lists, which together must equal the set of `.amdhsa_kernel` symbols (tests/test_kernel_matrix.py asserts it in both directions):
 
@@ -10,8 +16,8 @@ Three lists, which together must equal the set of `.amdhsa_kernel` symbols (test
                forces it (where one is needed), the shape, and the plan fields that select it as the plan QUERY reports them.  The GPU
                part of tests/test_kernel_matrix.py runs every case and first asserts that the query, read on that device, selects the
                claimed instantiation.
-  OTHER        every other kernel (schedule, scan, reduce, finish, predict, STRICT, pair_forces_clocked), once, with the existing test
-               that checks it.
+  OTHER        every other kernel (schedule, scan, reduce, finish, predict, pack, sync, STRICT, pair_forces_clocked, pair_forces_jpacked),
+               once per listing, with the existing test that checks it.
   UNREACHABLE  instantiations no public call can launch, each with the host-side reason, which is asserted.  None of them can be
                selected by a default plan (no override) for any N: that is asserted too.
 
@@ -29,13 +35,19 @@ DTYPE_OF = {"float": F32, "double": F64}
 LANE_WIDTH = {F32: 2, F64: 1}  # W: bodies i per vector (fp32 travels in packed pairs)
 
 LISTINGS = ("nbody_fast.s", "nbody_strict.s", "nbody_pair.s", "nbody_energy.s", "ensemble_fast.s", "ensemble_strict.s", "hermite_eval.s", "hermite_block.s",
-            "neighbour.s", "energy_ensemble.s")
-UNREGISTERED = ("field.s", "knn.s", "nbody_pair_lead.s", "hermite_ensemble.s", "hermite_block_ensemble.s", "hermite6_eval.s", "hermite6_block.s", "hermite6_ensemble.s",
-                "hermite6_block_ensemble.s")  # built by the Makefile, out of scope here
+            "neighbour.s", "energy_ensemble.s", "hermite6_eval.s", "hermite6_block.s", "hermite_block_ensemble.s", "hermite6_block_ensemble.s", "nbody_pair_lead.s")
+# listing -> (test module, the function that returns its registry); the module also has test_every_kernel_of_the_listing_is_in_the_registry
+REGISTERED_ELSEWHERE = {
+    "field.s": ("tests.test_field", "field_registry"),
+    "knn.s": ("tests.test_knn", "knn_registry"),
+    "hermite_ensemble.s": ("tests.test_hermite_ensemble", "ensemble_registry"),
+    "hermite6_ensemble.s": ("tests.test_hermite6_ensemble", "ensemble6_registry"),
+}
+LISTING_TEST = "test_every_kernel_of_the_listing_is_in_the_registry"
 
 # ---------------------------------------------------------------------------------------------------------------- symbols
 _PREFIX = re.compile(r"^_ZN2nb12_GLOBAL__N_1(\d+)")
-_TEMPLATE = re.compile(r"^I([fd])((?:L[ib]\d+E)*)E")
+_TEMPLATE = re.compile(r"^I([fd]?)((?:L[ib]\d+E)*)E")  # (no T: pair_forces_jpacked<8>)
 _ARGUMENT = re.compile(r"L([ib])(\d+)E")
 _DEMANGLED = re.compile(r"nb::\(anonymous namespace\)::(\w+)(?:<([^>]*)>)?\(")
 
@@ -47,8 +59,8 @@ def parse_symbol(symbol):
         start, length = m.end(), int(m.group(1))
         name, rest = symbol[start:start + length], symbol[start + length:]
         t = _TEMPLATE.match(rest)
-        if t:
-            args = [TYPE_NAME[F32 if t.group(1) == "f" else F64]]
+        if t and (t.group(1) or t.group(2)):
+            args = [TYPE_NAME[F32 if t.group(1) == "f" else F64]] if t.group(1) else []
             args += [bool(int(v)) if k == "b" else int(v) for k, v in _ARGUMENT.findall(t.group(2))]
             return name, tuple(args)
         if rest.startswith("E"):
@@ -104,6 +116,10 @@ class Case:
     @property
     def kernel(self):
         return self.family, (TYPE_NAME[self.dtype], *self.args)
+
+    @property
+    def listing(self):
+        return FAMILY_LISTING[self.family]
 
     @property
     def id(self):
@@ -169,11 +185,12 @@ def _pair_cases():
 
 
 # The libraries dispatched by N alone: S, the waves that split j, is 1 below 256 bodies, 2 from 256, 4 from 512, 8 from 1 024
-# (plan_ensemble_fast, plan_stream, block_waves, neighbour_waves).  The sizes sit on and around every switch point -- a wave gets exactly
+# (plan_ensemble_fast, plan_stream, block_waves, neighbour_waves; the 6th-order and block-ensemble units take plan_stream and block_waves).  The sizes sit on and around every switch point -- a wave gets exactly
 # one chunk, then one chunk and one ragged body -- and inside the S = 4 window.
 N_BY_WAVES = {1: (255,), 2: (256, 257, 511), 4: (512, 513, 700, 1023), 8: (1024, 1025)}
 MASSES = ("equal", "species", "random")
 ENSEMBLE_LARGE = ((8192 + 37, 3), (65536, 2))  # (bodies, systems), S = 8: the fp32 second-level sums fire from 8 192 bodies; the API's largest N
+BLOCK_ENSEMBLE_SYSTEMS = 3  # one system per kind of MASSES, with 1, 129 and all bodies due
 
 
 def ensemble_vectors(dtype, waves):
@@ -197,6 +214,13 @@ def _n_dispatched_cases():
                 for pot in (False, True):
                     out.append(Case("neighbour_survey", dtype, (s, pot), "nb_neighbour_survey", (), (("waves_per_group", s),), (("n", n),),
                                     "POT = false: the survey of distances and counts (and the lists built on it); true: with potentials"))
+                # the 6th-order scheme: the same driver text with nine sums, an interaction and a finish of its own
+                for step in (False, True):
+                    out.append(Case("hermite6_eval", dtype, (s, step), "nb_hermite6_step" if step else "nb_hermite6_eval", (), (("waves_per_group", s),), (("n", n),)))
+                out.append(Case("hermite6_block_eval", dtype, (s,), "nb_hermite6_block_step", (), (("waves_per_group", s),), (("n", n),)))
+                # the block steps of many systems: three systems of n bodies, bit for bit the solo steps (which the cases above hold to long double)
+                for family, entry in (("hermite_block_ensemble_eval", "nb_hermite_block_ensemble_step"), ("hermite6_block_ensemble_eval", "nb_hermite6_block_ensemble_step")):
+                    out.append(Case(family, dtype, (s,), entry, (), (("waves_per_group", s),), (("n", n), ("systems", BLOCK_ENSEMBLE_SYSTEMS))))
     return out
 
 
@@ -222,8 +246,15 @@ def _energy_ensemble_cases():
 
 
 CASES = _stream_cases() + _wavesplit_cases() + _pair_cases() + _n_dispatched_cases() + _energy_ensemble_cases()
-FAMILIES = ("integrate_bodies_fast", "integrate_bodies_wavesplit", "pair_forces", "ensemble_fast", "hermite_eval", "hermite_block_eval", "neighbour_survey",
-            "energy_ensemble_pairs")
+# family -> the one listing that holds its instantiations
+FAMILY_LISTING = {"integrate_bodies_fast": "nbody_fast.s", "integrate_bodies_wavesplit": "nbody_fast.s", "pair_forces": "nbody_pair.s", "ensemble_fast": "ensemble_fast.s",
+                  "hermite_eval": "hermite_eval.s", "hermite_block_eval": "hermite_block.s", "neighbour_survey": "neighbour.s", "energy_ensemble_pairs": "energy_ensemble.s",
+                  "hermite6_eval": "hermite6_eval.s", "hermite6_block_eval": "hermite6_block.s", "hermite_block_ensemble_eval": "hermite_block_ensemble.s",
+                  "hermite6_block_ensemble_eval": "hermite6_block_ensemble.s"}
+FAMILIES = tuple(FAMILY_LISTING)
+# the families whose S follows N alone (N_BY_WAVES), with the position of S among the template arguments after T
+N_DISPATCHED = {"ensemble_fast": 1, "hermite_eval": 0, "hermite_block_eval": 0, "neighbour_survey": 0, "hermite6_eval": 0, "hermite6_block_eval": 0,
+                "hermite_block_ensemble_eval": 0, "hermite6_block_ensemble_eval": 0}
 
 
 def cases_of(family):
@@ -231,7 +262,7 @@ def cases_of(family):
 
 
 def claimed_kernels():
-    return {c.kernel for c in CASES}
+    return {(c.listing, c.kernel) for c in CASES}
 
 
 # ---------------------------------------------------------------------------------------------------------------- every other kernel
@@ -239,33 +270,101 @@ def _both(name, test):
     return {(name, ("float",)): test, (name, ("double",)): test}
 
 
+def _in(listing, kernels):
+    return {(listing, kernel): test for kernel, test in kernels.items()}
+
+
+_BLOCK4 = "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double"
+_BLOCK6 = "tests.test_hermite6_block::test_one_block6_step_stage_by_stage_against_long_double"
+# a block-ensemble kernel outside the evaluation is held to the solo call's bits, array by array and status by status, and the solo kernels to
+# long double by the solo entries above it; the summary is recomputed from the statuses in the same test (check_against_solo)
+_ENSEMBLE4, _ENSEMBLE6 = "tests.test_hermite_block_ensemble", "tests.test_hermite6_block_ensemble"
+_STEP_BITS, _INIT_SYNC_BITS = "test_three_systems_take_the_solo_steps_bit_for_bit", "test_init_and_sync_are_the_solo_calls_per_system"
+
+
+def _block_ensemble(module, predict_count, finish, sync):
+    return {
+        ("block_ensemble_summary", ()): f"{module}::{_STEP_BITS}",
+        **_both("block_ensemble_init_levels", f"{module}::{_INIT_SYNC_BITS}"),
+        **_both("block_ensemble_min_partial", f"{module}::{_STEP_BITS}"),
+        **_both(predict_count, f"{module}::{_STEP_BITS}"),
+        **_both("block_ensemble_scatter", f"{module}::{_STEP_BITS}"),
+        **_both(finish, f"{module}::{_STEP_BITS}"),
+        **_both(sync, f"{module}::{_INIT_SYNC_BITS}"),
+    }
+
+
 OTHER = {
-    **_both("integrate_bodies_strict", "tests.test_gpu_parity::test_strict_matches_oracle_bitwise_ragged"),
-    **_both("ensemble_strict", "tests.test_ensemble::test_strict_every_system_matches_the_oracle"),
-    **_both("energy_pairs", "tests.test_energy::test_energy_matches_fp64_numpy"),
-    ("energy_finish", ()): "tests.test_energy::test_energy_matches_fp64_numpy",
-    **_both("pair_finish", "tests.test_pairwise::test_pair_mass_forms"),
-    **_both("pair_reduce", "tests.test_pairwise::test_sliced_pairwise_force_error"),
-    ("pair_forces_clocked", ("float", 8, 8)): "tests.test_pairwise::test_clocked_variant_of_the_forces_kernel_changes_no_bit",
-    ("pair_forces_clocked", ("double", 8, 8)): "tests.test_pairwise::test_clocked_variant_of_the_forces_kernel_changes_no_bit",
-    **_both("hermite_predict", "tests.test_hermite::test_one_step_against_long_double"),
-    **_both("hermite_timestep_partial", "tests.test_hermite::test_shared_time_step"),
-    **_both("hermite_timestep_final", "tests.test_hermite::test_shared_time_step"),
-    ("block_min_partial", ()): "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double",
-    **_both("block_predict_count", "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double"),
-    ("block_scan", ()): "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double",
-    ("block_scatter", ()): "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double",
-    **_both("hermite_block_finish", "tests.test_hermite_block::test_one_block_step_stage_by_stage_against_long_double"),
-    **_both("block_init_levels", "tests.test_hermite_block::test_init_levels_against_long_double"),
-    **_both("block_sync", "tests.test_hermite_block::test_python_class_gives_the_c_calls_bits"),
-    ("neighbour_status", ()): "tests.test_neighbour::test_exact_lattices",
-    **_both("neighbour_count", "tests.test_neighbour::test_exact_lattices"),
-    ("list_block", ()): "tests.test_neighbour::test_exact_lattices",
-    ("list_scan", ()): "tests.test_neighbour::test_exact_lattices",
-    ("list_offsets", ()): "tests.test_neighbour::test_exact_lattices",
-    **_both("neighbour_fill", "tests.test_neighbour::test_exact_lattices"),
-    ("energy_ensemble_finish", ()): "tests.test_energy_ensemble::test_every_system_matches_fp64_numpy",
-    ("energy_ensemble_drift_summary", ()): "tests.test_energy_ensemble::test_drift_summary_agrees_with_numpy",
+    **_in("nbody_strict.s", _both("integrate_bodies_strict", "tests.test_gpu_parity::test_strict_matches_oracle_bitwise_ragged")),
+    **_in("ensemble_strict.s", _both("ensemble_strict", "tests.test_ensemble::test_strict_every_system_matches_the_oracle")),
+    **_in("nbody_energy.s", {
+        **_both("energy_pairs", "tests.test_energy::test_energy_matches_fp64_numpy"),
+        ("energy_finish", ()): "tests.test_energy::test_energy_matches_fp64_numpy",
+    }),
+    **_in("nbody_pair.s", {
+        **_both("pair_finish", "tests.test_pairwise::test_pair_mass_forms"),
+        **_both("pair_reduce", "tests.test_pairwise::test_sliced_pairwise_force_error"),
+        ("pair_forces_clocked", ("float", 8, 8)): "tests.test_pairwise::test_clocked_variant_of_the_forces_kernel_changes_no_bit",
+        ("pair_forces_clocked", ("double", 8, 8)): "tests.test_pairwise::test_clocked_variant_of_the_forces_kernel_changes_no_bit",
+    }),
+    # one S is compiled (launch_pair_lead): not a family.  What selects it is JPACKED_PLAN, asserted on the host at JPACKED_N
+    **_in("nbody_pair_lead.s", {("pair_forces_jpacked", (8,)): "tests.test_pair_jpacked::test_jpacked_shapes"}),
+    **_in("hermite_eval.s", {
+        **_both("hermite_predict", "tests.test_hermite::test_one_step_against_long_double"),
+        **_both("hermite_timestep_partial", "tests.test_hermite::test_shared_time_step"),
+        **_both("hermite_timestep_final", "tests.test_hermite::test_shared_time_step"),
+    }),
+    **_in("hermite_block.s", {
+        ("block_min_partial", ()): _BLOCK4,
+        **_both("block_predict_count", _BLOCK4),
+        ("block_scan", ()): _BLOCK4,
+        ("block_scatter", ()): _BLOCK4,
+        **_both("hermite_block_finish", _BLOCK4),
+        **_both("block_init_levels", "tests.test_hermite_block::test_init_levels_against_long_double"),
+        **_both("block_sync", "tests.test_hermite_block::test_python_class_gives_the_c_calls_bits"),
+    }),
+    **_in("neighbour.s", {
+        ("neighbour_status", ()): "tests.test_neighbour::test_exact_lattices",
+        **_both("neighbour_count", "tests.test_neighbour::test_exact_lattices"),
+        ("list_block", ()): "tests.test_neighbour::test_exact_lattices",
+        ("list_scan", ()): "tests.test_neighbour::test_exact_lattices",
+        ("list_offsets", ()): "tests.test_neighbour::test_exact_lattices",
+        **_both("neighbour_fill", "tests.test_neighbour::test_exact_lattices"),
+    }),
+    **_in("energy_ensemble.s", {
+        ("energy_ensemble_finish", ()): "tests.test_energy_ensemble::test_every_system_matches_fp64_numpy",
+        ("energy_ensemble_drift_summary", ()): "tests.test_energy_ensemble::test_drift_summary_agrees_with_numpy",
+    }),
+    **_in("hermite6_eval.s", {
+        **_both("hermite6_pack", "tests.test_hermite6::test_eval_against_long_double_sums"),
+        **_both("hermite6_predict", "tests.test_hermite6::test_one_step_against_long_double"),
+        **_both("hermite6_timestep_partial", "tests.test_hermite6::test_time_step"),
+        **_both("hermite6_timestep_final", "tests.test_hermite6::test_time_step"),
+    }),
+    **_in("hermite6_block.s", {
+        ("block_min_partial", ()): _BLOCK6,
+        **_both("block6_predict_count", _BLOCK6),
+        ("block_scan", ()): _BLOCK6,
+        ("block_scatter", ()): _BLOCK6,
+        **_both("hermite6_block_finish", _BLOCK6),
+        **_both("block6_init_levels", "tests.test_hermite6_block::test_block6_init_is_hermite6_init_and_levels_against_long_double"),
+        **_both("block6_sync", "tests.test_hermite6_block::test_block6_python_class_gives_the_c_calls_bits"),
+    }),
+    **_in("hermite_block_ensemble.s", _block_ensemble(_ENSEMBLE4, "block_ensemble_predict_count", "hermite_block_ensemble_finish", "block_ensemble_sync")),
+    **_in("hermite6_block_ensemble.s", _block_ensemble(_ENSEMBLE6, "block6_ensemble_predict_count", "hermite6_block_ensemble_finish", "block6_ensemble_sync")),
+}
+
+# pair_forces_jpacked: the geometry nb_set_pair_plan_override(8, 8, 1, 1) forces, as the plan query reports it -- what one_step of
+# tests/test_pair_jpacked.py asserts before every launch -- at the size of test_jpacked_shapes whose last tile's second half holds one body
+JPACKED_OVERRIDE = ("set_pair_plan_override", (8, 8, 1, 1))
+JPACKED_PLAN = (("applies", 1), ("slices", 1), ("bodies_per_lane", 16), ("waves_per_block", 8), ("splits", 1))
+JPACKED_N = 3072 + 65
+
+# the kernels compiled into more than one listing, under one symbol: whole kernels shared as text by the block-step units
+SHARED_TEXT = {
+    **{(name, ()): ("hermite_block.s", "hermite6_block.s") for name in ("block_min_partial", "block_scan", "block_scatter")},  # hermite_block_schedule.inc
+    **{kernel: ("hermite_block_ensemble.s", "hermite6_block_ensemble.s")  # hermite_block_ensemble_schedule.inc
+       for kernel in (("block_ensemble_summary", ()), *_both("block_ensemble_init_levels", ""), *_both("block_ensemble_min_partial", ""), *_both("block_ensemble_scatter", ""))},
 }
 
 
@@ -310,14 +409,15 @@ UNREACHABLE = [
 
 
 def registry():
-    """kernel -> what the registry says about it; raises if a kernel is named twice"""
+    """(listing, kernel) -> what the registry says about it; raises if a kernel of a listing is named twice"""
     out = {}
-    for kernel in sorted(claimed_kernels()):
-        out[kernel] = "cases"
-    for kernel in OTHER:
-        assert kernel not in out, kernel_name(kernel)
-        out[kernel] = "other"
+    for key in sorted(claimed_kernels()):
+        out[key] = "cases"
+    for key in OTHER:
+        assert key not in out, (key[0], kernel_name(key[1]))
+        out[key] = "other"
     for u in UNREACHABLE:
-        assert u.kernel not in out, kernel_name(u.kernel)
-        out[u.kernel] = "unreachable"
+        key = (FAMILY_LISTING[u.kernel[0]], u.kernel)
+        assert key not in out, kernel_name(u.kernel)
+        out[key] = "unreachable"
     return out

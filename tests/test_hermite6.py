@@ -532,7 +532,12 @@ def ld_step(pos, vel, acc, jerk, snap, crackle, dt, eps2, predicted):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("n,mass", [(65, "equal"), (65, "random"), (1000, "equal"), (1000, "random"), (300, "equal"), (600, "equal"), (1100, "equal")])
 def test_one_step_against_long_double(gpu, n, mass, dtype):
-    """the second step of a run (so that the crackle the predictor reads is not 0), stage by stage"""
+    check_one_step6(gpu, dtype, n, mass)
+
+
+def check_one_step6(gpu, dtype, n, mass):
+    """the second step of a run of cloud(n, mass) (so that the crackle the predictor reads is not 0) against ld_step, stage by stage; shared
+    with tests/test_kernel_matrix.py"""
     pos, vel = cloud(n, dtype, 31 + n, mass)
     eps2, dt = dtype(0.01), dtype(1.0 / 64)
     d = Device(gpu, pos, vel, eps2)

@@ -1,15 +1,19 @@
 """Every compiled kernel instantiation against a long double sum (the registry: tests/kernel_matrix.py).
 
-CPU part: the ten registered listings of `make asm` (the nine of the step, Hermite and neighbour kernels, and energy_ensemble.s; the Makefile's
-other nine are named as out of scope) hold exactly the kernels the registry names -- a new `case` in a dispatch switch, or a case taken
-out of the registry, fails here with the kernel's name -- and every case's shape makes the plan query select the instantiation it claims
-(the one-sided and pairwise queries with the CU count a machine without a device reports; the GPU part reads them again on the device).
+CPU part: the fifteen registered listings of `make asm` (the step, pairwise, Hermite, block-step, block-ensemble and neighbour kernels of
+both orders, and energy_ensemble.s) hold exactly the kernels the registry names, listing by listing -- a new `case` in a dispatch switch,
+or a case taken out of the registry, fails here with the kernel's name -- and every case's shape makes the plan query select the
+instantiation it claims (the one-sided and pairwise queries with the CU count a machine without a device reports; the GPU part reads them
+again on the device).  The Makefile's other four listings (field.s, knn.s, hermite_ensemble.s, hermite6_ensemble.s) are registered in the
+test modules of their libraries: kernel_matrix.REGISTERED_ELSEWHERE names module and registry function, resolved and asserted here.
 
 GPU part: one parametrised test per shape-dispatched family, one parameter per case: set the override, assert that the plan query selects
 the claimed instantiation, run it through the public entry point, restore the override, and compare with long double sums -- the
 project's own references and bounds, imported from the modules that define them (test_gpu_parity.direct_sum_f64, test_fast_domain's TOL,
-UNIT_ROUNDOFF and check_step, the checkers of test_hermite, test_hermite_block and test_neighbour; for energy_ensemble_pairs the probe
-pairs and probe bodies of test_energy_domain, which count every pair and every body once, bit for bit).
+UNIT_ROUNDOFF and check_step, the checkers of test_hermite, test_hermite_block, test_hermite6, test_hermite6_block and test_neighbour;
+for energy_ensemble_pairs the probe pairs and probe bodies of test_energy_domain, which count every pair and every body once, bit for
+bit; for the two block ensembles the solo block steps' bits, the solo kernels being held to long double at the same sizes by the cases
+of hermite_block_eval and hermite6_block_eval).
 
 How a one-sided case sizes its ranges (nb_integrate_shard_*, i and j independent) is in stream_launches / wavesplit_launches below: each
 instantiation meets a ragged i range that does not start at 0, a j range that starts off a multiple of 4, a ragged last chunk with an odd
@@ -17,13 +21,19 @@ number of groups, fewer chunks than waves, in fp32 enough chunks per wave for th
 first body j of mass zero."""
 import ctypes
 import hashlib
+import importlib
 import os
 import subprocess
+from collections import Counter
 
 import numpy as np
 import pytest
 
 import kernel_matrix as km
+import test_hermite6 as hermite6
+import test_hermite6_block as block6
+import test_hermite6_block_ensemble as block6_ensemble
+import test_hermite_block_ensemble as block_ensemble
 from conftest import ROOT
 from test_ensemble import T as as_T
 from test_ensemble import eps2_of, step as ensemble_step, systems as ensemble_systems
@@ -66,38 +76,75 @@ def test_symbol_parser_reads_template_arguments():
     assert km.parse_symbol("_ZN2nb12_GLOBAL__N_110block_scanEPjjPNS_9BlockCtrlEPNS_11BlockStatusE") == ("block_scan", ())
     assert km.parse_symbol("_ZN2nb12_GLOBAL__N_113energy_finishEPKdjP9nb_energy") == ("energy_finish", ())
     assert km.kernel_name(("hermite_eval", ("float", 4, False))) == "hermite_eval<float, 4, false>"
+    assert km.parse_symbol("_ZN2nb12_GLOBAL__N_119pair_forces_jpackedILi8EEEvNS_8PairArgsIfEE") == ("pair_forces_jpacked", (8,))
+    assert km.parse_demangled("void nb::(anonymous namespace)::pair_forces_jpacked<8>(nb::PairArgs<float>)") == ("pair_forces_jpacked", (8,))
+    assert km.parse_symbol("_ZN2nb12_GLOBAL__N_113hermite6_evalIdLi8ELb1EEEvNS_12Hermite6ArgsIT_EE") == ("hermite6_eval", ("double", 8, True))
+
+
+def named(keys):
+    return sorted(f"{listing}: {km.kernel_name(kernel)}" for listing, kernel in keys)
 
 
 def test_the_listings_and_the_registry_name_the_same_kernels():
-    """both directions, by name: a compiled kernel the registry does not know; a kernel the registry names that is not compiled"""
+    """both directions, by listing and name: a compiled kernel the registry does not know; a kernel the registry names that is not compiled"""
     with open(os.path.join(CSRC, "Makefile")) as f:
         built = next(line for line in f if line.startswith("ASM :=")).split()[2:]
-    assert len(km.LISTINGS) == 10 and len(km.UNREGISTERED) == 9 and sorted(km.LISTINGS + km.UNREGISTERED) == sorted(built), "a listing neither registered nor named as out of scope"
-    compiled = [k for kernels in listed().values() for k in kernels]
-    assert len(compiled) == len(set(compiled)), "a kernel is compiled into two listings"
+    assert not hasattr(km, "UNREGISTERED"), "every listing is registered, here or in its library's module"
+    assert len(km.LISTINGS) == 15 and len(km.REGISTERED_ELSEWHERE) == 4 and not set(km.LISTINGS) & set(km.REGISTERED_ELSEWHERE)
+    assert sorted(km.LISTINGS + tuple(km.REGISTERED_ELSEWHERE)) == sorted(built), "a listing in neither table, or a table naming a listing the Makefile does not build"
+    compiled = [(listing, k) for listing, kernels in listed().items() for k in kernels]
+    twice = {key: count for key, count in Counter(compiled).items() if count > 1}
+    assert not twice, f"a listing holds a symbol twice: {named(twice)}"
+    # the same symbol in two listings: whole kernels shared as text, each copy registered with a test of its own library -- exactly SHARED_TEXT
+    where = {}
+    for listing, kernel in compiled:
+        where.setdefault(kernel, []).append(listing)
+    shared = {kernel: tuple(sorted(listings)) for kernel, listings in where.items() if len(listings) > 1}
+    assert shared == {kernel: tuple(sorted(listings)) for kernel, listings in km.SHARED_TEXT.items()}, \
+        f"compiled into more than one listing, against kernel_matrix.SHARED_TEXT: {sorted(km.kernel_name(k) for k in set(shared) ^ set(km.SHARED_TEXT))}"
+    assert not any(kernel[0] in km.FAMILIES for kernel in shared), "an instantiation of a shape-dispatched family belongs to one listing"
     registry = km.registry()
-    unknown = sorted(km.kernel_name(k) for k in set(compiled) - set(registry))
+    unknown = named(set(compiled) - set(registry))
     assert not unknown, f"compiled, but in no list of tests/kernel_matrix.py (CASES, OTHER, UNREACHABLE): {unknown}"
-    missing = sorted(km.kernel_name(k) for k in set(registry) - set(compiled))
-    assert not missing, f"named by tests/kernel_matrix.py, but in no listing: {missing}"
+    missing = named(set(registry) - set(compiled))
+    assert not missing, f"named by tests/kernel_matrix.py, but not in that listing: {missing}"
     # every instantiation of a shape-dispatched family is claimed by a case, unless UNREACHABLE says why not
     unreachable = {u.kernel for u in km.UNREACHABLE}
-    for kernel in compiled:
+    for listing, kernel in compiled:
         if kernel[0] in km.FAMILIES and kernel not in unreachable:
-            assert registry[kernel] == "cases", f"{km.kernel_name(kernel)}: an instantiation of a shape-dispatched family without a case"
+            assert listing == km.FAMILY_LISTING[kernel[0]], (listing, km.kernel_name(kernel))
+            assert registry[listing, kernel] == "cases", f"{km.kernel_name(kernel)}: an instantiation of a shape-dispatched family without a case"
         if kernel[0] not in km.FAMILIES:
-            assert registry[kernel] == "other", km.kernel_name(kernel)
-    sizes = {family: sum(1 for k in compiled if k[0] == family) for family in km.FAMILIES}
+            assert registry[listing, kernel] == "other", (listing, km.kernel_name(kernel))
+    sizes = {family: sum(1 for _, k in compiled if k[0] == family) for family in km.FAMILIES}
     assert sizes == {"integrate_bodies_fast": 45, "integrate_bodies_wavesplit": 20, "pair_forces": 32, "ensemble_fast": 8, "hermite_eval": 16,
-                     "hermite_block_eval": 8, "neighbour_survey": 16, "energy_ensemble_pairs": 12}, sizes
+                     "hermite_block_eval": 8, "neighbour_survey": 16, "energy_ensemble_pairs": 12, "hermite6_eval": 16, "hermite6_block_eval": 8,
+                     "hermite_block_ensemble_eval": 8, "hermite6_block_ensemble_eval": 8}, sizes
+    # pair_forces_jpacked: one S, so a kernel of OTHER; a second S would make it a family with cases
+    assert [k for k in listed()["nbody_pair_lead.s"] if k[0] == "pair_forces_jpacked"] == [("pair_forces_jpacked", (8,))]
+
+
+def test_the_other_four_listings_have_registries_of_their_own():
+    """field.s, knn.s, hermite_ensemble.s and hermite6_ensemble.s: the module and the registry function kernel_matrix.REGISTERED_ELSEWHERE
+    names exist, the registry is not empty, and the module holds the test that compares it with its listing"""
+    for listing, (module_name, function) in km.REGISTERED_ELSEWHERE.items():
+        assert module_name.startswith("tests.") and os.path.exists(os.path.join(ROOT, *module_name.split(".")) + ".py"), (listing, module_name)
+        module = importlib.import_module(module_name.split(".", 1)[1])
+        assert callable(getattr(module, function, None)), f"{listing}: {module_name} has no {function}()"
+        assert len(getattr(module, function)()) > 0, f"{listing}: {module_name}.{function}() names no kernel"
+        assert callable(getattr(module, km.LISTING_TEST, None)), f"{listing}: {module_name} has no {km.LISTING_TEST}"
+        with open(module.__file__) as f:
+            text = f.read()
+        assert f'"{listing}"' in text, f"{module_name} does not read {listing}"
 
 
 def test_every_other_kernel_names_an_existing_test():
-    for kernel, test in km.OTHER.items():
+    for (listing, kernel), test in km.OTHER.items():
+        assert listing in km.LISTINGS, (listing, km.kernel_name(kernel))
         module, name = test.split("::")
         path = os.path.join(ROOT, *module.split(".")) + ".py"
         with open(path) as f:
-            assert f"\ndef {name}(" in f.read(), f"{km.kernel_name(kernel)}: {test} does not exist"
+            assert f"\ndef {name}(" in f.read(), f"{listing}: {km.kernel_name(kernel)}: {test} does not exist"
 
 
 def plan_fields(plan, case):
@@ -116,6 +163,14 @@ def query(pkg, case, n=None, i_count=None, j_count=None):
         return pkg.hermite_plan(n, case.dtype)
     if case.family == "hermite_block_eval":
         return pkg.hermite_block_plan(n, n, case.dtype)
+    if case.family == "hermite6_eval":
+        return pkg.hermite6_plan(n, case.dtype)
+    if case.family == "hermite6_block_eval":
+        return pkg.hermite6_block_plan(n, n, case.dtype)
+    if case.family == "hermite_block_ensemble_eval":
+        return pkg.hermite_block_ensemble_plan(n, dict(case.shape)["systems"], n, case.dtype)
+    if case.family == "hermite6_block_ensemble_eval":
+        return pkg.hermite6_block_ensemble_plan(n, dict(case.shape)["systems"], n, case.dtype)
     if case.family == "energy_ensemble_pairs":
         return pkg.energy_ensemble_plan(n, 1, case.dtype)
     return pkg.neighbour_plan(n, case.dtype)
@@ -138,28 +193,39 @@ class forced:
 
 
 def test_n_dispatched_cases_select_their_instantiation_on_the_host(pkg):
-    """ensemble, Hermite, block steps, neighbours: the plan is host logic of (N, precision) alone"""
+    """ensemble, Hermite and block steps of both orders, block ensembles, neighbours: the plan is host logic of (N, precision) alone"""
+    assert set(km.N_DISPATCHED) <= set(km.FAMILIES)
     for case in km.CASES:
-        if case.family not in ("ensemble_fast", "hermite_eval", "hermite_block_eval", "neighbour_survey"):
+        if case.family not in km.N_DISPATCHED:
             continue
         n = dict(case.shape)["n"]
         assert plan_fields(query(pkg, case, n=n), case) == case.plan, (case.id, n)
-        s = case.args[1] if case.family == "ensemble_fast" else case.args[0]
+        s = case.args[km.N_DISPATCHED[case.family]]
         assert n in km.N_BY_WAVES[s] or (case.family == "ensemble_fast" and (n, dict(case.shape)["systems"]) in km.ENSEMBLE_LARGE)
-    # every instantiation has a case at every size of its wave count: one taken out is missed by the kernel's name
-    for family in ("ensemble_fast", "hermite_eval", "hermite_block_eval", "neighbour_survey"):
-        for kernel in sorted({c.kernel for c in km.cases_of(family)}):
-            s = kernel[1][2] if family == "ensemble_fast" else kernel[1][1]
-            want = {(n, 3) for n in km.N_BY_WAVES[s]} | (set(km.ENSEMBLE_LARGE) if s == 8 else set()) if family == "ensemble_fast" else set(km.N_BY_WAVES[s])
-            have = {(dict(c.shape)["n"], dict(c.shape)["systems"]) if family == "ensemble_fast" else dict(c.shape)["n"] for c in km.cases_of(family) if c.kernel == kernel}
+    # every instantiation the listing holds has a case at every size of its wave count: one taken out is missed by the kernel's name
+    for family, position in km.N_DISPATCHED.items():
+        compiled = sorted(k for k in listed()[km.FAMILY_LISTING[family]] if k[0] == family)
+        assert compiled, family
+        for kernel in compiled:
+            s = kernel[1][1 + position]
+            with_systems = {"ensemble_fast": 3, "hermite_block_ensemble_eval": km.BLOCK_ENSEMBLE_SYSTEMS, "hermite6_block_ensemble_eval": km.BLOCK_ENSEMBLE_SYSTEMS}.get(family)
+            want = set(km.N_BY_WAVES[s]) if with_systems is None else {(n, with_systems) for n in km.N_BY_WAVES[s]}
+            if family == "ensemble_fast" and s == 8:
+                want |= set(km.ENSEMBLE_LARGE)
+            have = {dict(c.shape)["n"] if with_systems is None else (dict(c.shape)["n"], dict(c.shape)["systems"]) for c in km.cases_of(family) if c.kernel == kernel}
             assert have == want, f"{km.kernel_name(kernel)}: cases at {sorted(have)}, wanted at {sorted(want)}"
     # the switch points of S, and both neighbours of each
     for n in (255, 256, 257, 511, 512, 513, 1023, 1024, 1025):
         want = 1 if n < 256 else 2 if n < 512 else 4 if n < 1024 else 8
         for dtype in (F32, F64):
             got = (pkg.ensemble_plan(n, 1, dtype).waves_per_group, pkg.hermite_plan(n, dtype).waves_per_group, pkg.hermite_block_plan(n, 1, dtype).waves_per_group,
-                   pkg.neighbour_plan(n, dtype).waves_per_group)
-            assert got == (want,) * 4, (n, got)
+                   pkg.neighbour_plan(n, dtype).waves_per_group, pkg.hermite6_plan(n, dtype).waves_per_group, pkg.hermite6_block_plan(n, 1, dtype).waves_per_group,
+                   pkg.hermite_block_ensemble_plan(n, 1, 1, dtype).waves_per_group, pkg.hermite6_block_ensemble_plan(n, 1, 1, dtype).waves_per_group)
+            assert got == (want,) * 8, (n, got)
+            for n_act in (1, 65, 129, n):  # ... whatever part of the system is due
+                got = (pkg.hermite6_block_plan(n, n_act, dtype).waves_per_group, pkg.hermite_block_ensemble_plan(n, km.BLOCK_ENSEMBLE_SYSTEMS, n_act, dtype).waves_per_group,
+                       pkg.hermite6_block_ensemble_plan(n, km.BLOCK_ENSEMBLE_SYSTEMS, n_act, dtype).waves_per_group)
+                assert got == (want,) * 3, (n, n_act, got)
     # the energies of an ensemble: every case at the first or the last n of its window, every window with both, and every n from 1 to
     # 65 536 inside the window of the instantiation its plan selects -- so of the twelve compiled kernels only the ten with a case are ever
     # asked for (the other two: UNREACHABLE, test_unreachable_reasons_hold)
@@ -193,6 +259,15 @@ def test_overridden_cases_select_their_instantiation_on_the_host(pkg):
     for case in km.cases_of("pair_forces"):
         with forced(pkg, case.override):
             assert plan_fields(query(pkg, case, n=dict(case.shape)["n"]), case) == case.plan, case.id
+    # pair_forces_jpacked (OTHER): the geometry its test forces is the one launch_pair hands to it -- fp32, R = 8, eight waves, one split, one slice
+    assert km.OTHER["nbody_pair_lead.s", ("pair_forces_jpacked", (8,))] == "tests.test_pair_jpacked::test_jpacked_shapes"
+    import test_pair_jpacked  # (every test of it is marked gpu; its constants are plain)
+    sizes = next(mark.args[1] for mark in test_pair_jpacked.test_jpacked_shapes.pytestmark if mark.name == "parametrize")
+    assert km.JPACKED_OVERRIDE[1] == (*test_pair_jpacked.LEAD, 1) and km.JPACKED_N in sizes, "the override and a size of test_jpacked_shapes"
+    with forced(pkg, km.JPACKED_OVERRIDE):
+        for n in sizes:
+            p = pkg.pair_plan(n, F32)
+            assert tuple((name, getattr(p, name)) for name, _ in km.JPACKED_PLAN) == km.JPACKED_PLAN, f"{n} bodies: the forced headline geometry is not the j-packed kernel's"
 
 
 def test_unreachable_reasons_hold(pkg):
@@ -550,6 +625,92 @@ def test_hermite_block_eval(gpu, case):
     for k, (mass, n_act) in enumerate(zip(km.MASSES, (n, 129, 65))):
         assert plan_fields(gpu.hermite_block_plan(n, n_act, dtype), case) == case.plan, (case.id, n_act)
         check_block_stages(gpu, dtype, n, n_act, mass, (2e-5, 3e-4, 4e-3, 0.05)[(n + k) % 4])
+
+
+def step6_masses(case):
+    """The mass kinds of a hermite6_eval<T, S, true> case: one kind, rotating with the place of n among the sizes of its S -- or as many more
+    as it takes for the S with fewer than three sizes to meet all three (S = 1: one size, three kinds; S = 8: two sizes, two kinds each)."""
+    sizes = km.N_BY_WAVES[case.args[0]]
+    place = sizes.index(dict(case.shape)["n"])
+    return tuple(km.MASSES[(place + k) % 3] for k in range(-(-3 // len(sizes))))
+
+
+def test_every_wave_count_of_the_sixth_order_step_meets_every_mass_kind():
+    for dtype in (F32, F64):
+        for s in km.N_BY_WAVES:
+            cases = [c for c in km.cases_of("hermite6_eval") if c.dtype == dtype and c.args == (s, True)]
+            assert {m for c in cases for m in step6_masses(c)} == set(km.MASSES), (km.TYPE_NAME[dtype], s)
+            assert all(len(step6_masses(c)) == 1 for c in cases) or len(cases) < 3
+
+
+@gpu_only
+@pytest.mark.parametrize("case", km.cases_of("hermite6_eval"), ids=ids(km.cases_of("hermite6_eval")))
+def test_hermite6_eval(gpu, case):
+    """STEP = false: nb_hermite6_eval_* on the fp32-representable states of tests/test_hermite6.py (a random acc_in) with all three mass kinds,
+    against reference6 under check_eval.  STEP = true: the second step of a run, every stage against ld_step (check_one_step6), the mass
+    kinds in rotation over the sizes of an S (step6_masses).
+
+    What these cases found: with the corrector as first written (v + fma(h/2, a0 + a1, fma(h^3/120, s0 + s1, -h^2/10 (j1 - j0)))) the fp64
+    step with random masses had its worst velocity at 1.22 (n = 255) and 1.12 (n = 1025) of ld_step's bound, the evaluation being at 0.16
+    of its own; the module's case at n = 1000 passed at 0.984.  In these clouds (masses up to 8, softening 0.1, h = 1/64) a few bodies are
+    in encounters so tight that h^3/120 |s0 + s1| is the largest term of their velocity increment and larger than |v|, and every operation
+    on that term's path left a rounding of its size: four, against the 2u of the term magnitudes ld_step allows.  csrc/hermite6_correct.inc
+    now sums the increments of v1 and x1 in twice T's precision (fp32 in fp64, fp64 in double-double), so each takes one rounding of its
+    own size."""
+    n, dtype = dict(case.shape)["n"], case.dtype
+    assert plan_fields(gpu.hermite6_plan(n, dtype), case) == case.plan, case.id
+    if case.args[1]:
+        for mass in step6_masses(case):
+            hermite6.check_one_step6(gpu, dtype, n, mass)
+        return
+    eps2 = dtype(np.float32(EPS2))  # (the same eps^2 in both precisions: they share one long double reference)
+    for mass in km.MASSES:
+        pos, vel, acc = hermite6.state32(n, dtype, 6000 + n, mass, 0.3)
+        hermite6.check_eval(hermite6.evaluate(gpu, pos, vel, acc, eps2), pos, vel, acc, eps2, f"{case.id} {mass}")
+
+
+@gpu_only
+@pytest.mark.parametrize("case", km.cases_of("hermite6_block_eval"), ids=ids(km.cases_of("hermite6_block_eval")))
+def test_hermite6_block_eval(gpu, case):
+    """6th-order block-step stages with all, 129 and 65 of the bodies due (one, some and few tiles of active bodies): the predictor, the nine
+    sums against reference6, the corrector, the planes in range order bit for bit and the level decisions (check_block6_stages_of, whose
+    cap on decisions near a threshold counts these cases with the module's own)"""
+    n, dtype = dict(case.shape)["n"], case.dtype
+    for k, (mass, n_act) in enumerate(zip(km.MASSES, (n, 129, 65))):
+        assert plan_fields(gpu.hermite6_block_plan(n, n_act, dtype), case) == case.plan, (case.id, n_act)
+        pos, vel = cloud(n, dtype, 1000 + n + n_act, mass)
+        block6.check_block6_stages_of(gpu, pos, vel, dtype(0.01), n_act, mass, block6.STAGE_ETAS[(n + k) % 4])
+
+
+def check_block_ensemble_case(gpu, case, module, plan_query):
+    """Three systems of n bodies with equal, species and random masses and 1, 129 and n bodies due, each with a `now` of its own, in one call:
+    after 1 and after 12 block steps every array and the status of every system are the solo calls' bit for bit (check_against_solo of the
+    library's module)."""
+    n, systems, dtype = dict(case.shape)["n"], dict(case.shape)["systems"], case.dtype
+    actives = [1, min(129, n), n]
+    assert len(actives) == systems
+    for n_act in actives:
+        assert plan_fields(plan_query(n, systems, n_act, dtype), case) == case.plan, (case.id, n_act)
+    module.check_against_solo(gpu, dtype, n, actives)
+
+
+@gpu_only
+@pytest.mark.parametrize("case", km.cases_of("hermite_block_ensemble_eval"), ids=ids(km.cases_of("hermite_block_ensemble_eval")))
+def test_hermite_block_ensemble_eval(gpu, case):
+    """The solo block steps' bits (check_block_ensemble_case).  What makes bit equality a reference here: the solo kernels are held to long
+    double at these same sizes -- the predictor, the sums, the corrector and the level decisions -- by the cases of hermite_block_eval
+    above, so an ensemble instantiation that agrees with them bit for bit meets the same bounds, and one that folds its waves or ends its
+    last chunk otherwise does not agree."""
+    check_block_ensemble_case(gpu, case, block_ensemble, gpu.hermite_block_ensemble_plan)
+
+
+@gpu_only
+@pytest.mark.parametrize("case", km.cases_of("hermite6_block_ensemble_eval"), ids=ids(km.cases_of("hermite6_block_ensemble_eval")))
+def test_hermite6_block_ensemble_eval(gpu, case):
+    """The solo 6th-order block steps' bits (check_block_ensemble_case).  What makes bit equality a reference here: the solo kernels are
+    held to long double at these same sizes -- S = 4 and every switch of S included -- by the cases of hermite6_block_eval above; before
+    those cases the solo bits were themselves unreferenced between 512 and 1 023 bodies."""
+    check_block_ensemble_case(gpu, case, block6_ensemble, gpu.hermite6_block_ensemble_plan)
 
 
 @gpu_only

@@ -45,6 +45,7 @@ def main(trace_dir, out_path):
     for name in km.LISTINGS:
         with open(os.path.join(CSRC, name)) as f:
             listed += km.listed_kernels(f.read())
+    listed = list(dict.fromkeys(listed))  # a kernel two listings share as text (km.SHARED_TEXT) has one name in a trace: counted once
     files, seen, foreign = traced_kernels(trace_dir)
     unreachable = {u.kernel: u.reason for u in km.UNREACHABLE}
     dispatched = [k for k in listed if k[0] in km.FAMILIES]
